@@ -13,8 +13,10 @@ N>1 = configs[2]: 8 tablets x 12.5M rows sharded tablet->rank (strong
 scaling), final RCCL all-reduce of the partial aggregates over xGMI.
 
 Inputs are generated on host (seed 42) and resident in HBM before the timed
-region. The CPU baseline leg times the oracle (oracle/ — test infrastructure)
-on a bounded sample on this host; it is a reported baseline, not the target.
+region. A plain run sets up, warms up, times the steps and prints the result
+line. --full adds the CPU baseline leg, which times the oracle (oracle/ —
+test infrastructure) on this host; it is a reported baseline, not the target.
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 """
 import argparse
 import ctypes
@@ -54,6 +56,60 @@ def _cpu_worker(rng):
     return res.rows_scanned, res.rows_matched
 
 
+def _i64_words(a):
+    """int64 array -> float64 array with a trailing axis of (signed high
+    32 bits, unsigned low 32 bits): every int64 survives exactly, which a
+    direct float64 conversion does not promise above 2^53."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.int64)
+    return np.stack([(a >> 32).astype(np.float64),
+                     (a & 0xFFFFFFFF).astype(np.float64)], axis=-1)
+
+
+def _dump_outputs(dirpath, checksum, tablets, last_out, grouped, num_aggs):
+    """Write what the last timed step returned as DIR/<name>.npy, float64
+    throughout. Integer aggregates come twice: `<name>.npy` rounded to the
+    nearest double and `<name>_words.npy` exact (see _i64_words). Grouped
+    tables are sorted by group key (the device table's slot order is not
+    part of the result). A few MB at the most: nothing is sampled."""
+    import numpy as np
+    import ybgpu as y
+    os.makedirs(dirpath, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(dirpath, name + ".npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
+
+    merged = np.array(checksum, dtype=np.int64)
+    save("merged_aggs", merged)
+    save("merged_aggs_words", _i64_words(merged))
+    for t, out in zip(tablets, last_out):
+        pre = "tablet%d_" % t
+        if grouped:
+            keys, vals, cnts, n = out
+            k = np.frombuffer(keys, dtype=np.uint64, count=n)
+            v = np.frombuffer(vals, dtype=np.int64, count=n * y.MAX_AGGS)
+            c = np.frombuffer(cnts, dtype=np.uint64, count=n * y.MAX_AGGS)
+            order = np.argsort(k, kind="stable")
+            v = v.reshape(n, y.MAX_AGGS)[order, :num_aggs]
+            c = c.reshape(n, y.MAX_AGGS)[order, :num_aggs]
+            save(pre + "group_keys", k[order])
+            save(pre + "group_vals", v)
+            save(pre + "group_vals_words", _i64_words(v))
+            save(pre + "group_cnts", c)
+        else:
+            save(pre + "rows", [out.rows_scanned, out.rows_matched,
+                                out.entries_seen])
+            vi = np.array([out.aggs[a].value_i64 for a in range(num_aggs)],
+                          dtype=np.int64)
+            save(pre + "aggs", vi)
+            save(pre + "aggs_words", _i64_words(vi))
+            save(pre + "aggs_f64",
+                 [out.aggs[a].value_f64 for a in range(num_aggs)])
+            save(pre + "aggs_is_null",
+                 [out.aggs[a].is_null for a in range(num_aggs)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,8 +122,16 @@ def main():
                     help="filtersum = BASELINE configs[1]/[2]; mvcc = "
                          "configs[3] (5 versions/row, COUNT); groupby = "
                          "configs[4]-shaped grouped aggregate")
-    ap.add_argument("--cpu-sample-seconds", type=float, default=10.0)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline "
+                         "figure (the CPU-baseline leg)")
+    ap.add_argument("--cpu-sample-seconds", type=float, default=10.0,
+                    help="single-thread CPU sample budget (--full only)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU-baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -193,6 +257,10 @@ def main():
             2, dtype=torch.int64,
             device="cuda" if backend == "nccl" else "cpu")
 
+    # what the most recent step handed back per local tablet (references
+    # only — --dump-outputs reads them after the timed region)
+    last_out = [None] * len(my_tablets)
+
     def step():
         if group_col:
             # grouped partial aggregates; the cross-tablet merge of the
@@ -201,8 +269,9 @@ def main():
             import numpy as np
             total_sum = 0
             total_cnt = 0
-            for s in scans:
+            for i, s in enumerate(scans):
                 _keys, vals, cnts, _kb, n = s.group_aggregate_raw()
+                last_out[i] = (_keys, vals, cnts, n)
                 if n:
                     va = np.frombuffer(vals, dtype=np.int64,
                                        count=n * y.MAX_AGGS)
@@ -219,6 +288,7 @@ def main():
         for s in scans:
             s.execute()
         results = [s.aggregates() for s in scans]
+        last_out[:] = results
         total_sum = sum(r.aggs[0].value_i64 for r in results)
         total_cnt = sum(r.aggs[1].value_i64 for r in results)
         if dist is not None:
@@ -295,9 +365,14 @@ def main():
         except Exception:
             traffic = None
 
-    # ---- CPU baseline (oracle, rank 0, N=1 only) -------------------------
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, checksum, my_tablets, last_out,
+                      bool(group_col), len(aggs))
+
+    # ---- CPU baseline (--full; oracle, rank 0, N=1 only) -----------------
     cpu_baseline = None
-    if rank == 0 and world <= 1 and not args.skip_cpu_baseline:
+    if (args.full and rank == 0 and world <= 1
+            and not args.skip_cpu_baseline):
         data, offsets, nb, total, ne = first_tablet_data
         # calibrate on 256 blocks, then size the sample for the budget
         osc = y.orcl_schema_from(schema)

@@ -1,5 +1,5 @@
-import ctypes as C, struct, sys, time
-sys.path.insert(0, '/root/repo')
+import ctypes as C, os, struct, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ybgpu as y
 from gpu_scan import GpuScan
 schema = y.make_schema([y.KT_INT64], [(10, y.T_INT64, 1), (11, y.T_INT64, 1)], has_hash=False)
