@@ -54,6 +54,22 @@ def _lib():
                                           C.POINTER(C.c_double)]
     lib.yb_gpu_scan_close.restype = C.c_int
     lib.yb_gpu_scan_close.argtypes = [C.c_void_p]
+    lib.yb_gpu_scan_staged.restype = C.c_int
+    lib.yb_gpu_scan_staged.argtypes = [C.c_void_p]
+    lib.yb_gpu_snapshot_build.restype = C.c_int
+    lib.yb_gpu_snapshot_build.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.yb_gpu_snapshot_info.restype = C.c_int
+    lib.yb_gpu_snapshot_info.argtypes = [C.c_void_p,
+                                         C.POINTER(y.SnapshotInfo)]
+    lib.yb_gpu_snapshot_query.restype = C.c_int
+    lib.yb_gpu_snapshot_query.argtypes = [C.c_void_p,
+                                          C.POINTER(y.SnapshotQuery),
+                                          C.POINTER(y.ScanResult)]
+    lib.yb_gpu_snapshot_kernel_ms.restype = C.c_int
+    lib.yb_gpu_snapshot_kernel_ms.argtypes = [C.c_void_p,
+                                              C.POINTER(C.c_double)]
+    lib.yb_gpu_snapshot_close.restype = C.c_int
+    lib.yb_gpu_snapshot_close.argtypes = [C.c_void_p]
     lib.yb_gpu_last_error.restype = C.c_char_p
     lib.yb_gpu_available.restype = C.c_int
     return lib
@@ -192,7 +208,66 @@ class GpuScan:
                                             C.byref(decode)), "kernel_ms")
         return total.value, decode.value
 
+    def staged(self):
+        """True when the last execute was answered from a columnar snapshot
+        (YBG_STAGE=1 transparent mode)."""
+        return bool(self._lib.yb_gpu_scan_staged(self._h))
+
+    def snapshot(self):
+        """Build a columnar snapshot of the fed tablet at this handle's read
+        time and bounds (yb_gpu_snapshot_build). The snapshot owns its
+        memory: it stays valid after this handle is closed."""
+        h = C.c_void_p()
+        self._check(self._lib.yb_gpu_snapshot_build(self._h, C.byref(h)),
+                    "snapshot_build")
+        return GpuSnapshot(self._lib, h)
+
     def close(self):
         if self._h:
             self._lib.yb_gpu_scan_close(self._h)
+            self._h = None
+
+
+class GpuSnapshot:
+    """Columnar snapshot: the rows visible at one read time as dense
+    device-resident column arrays, answering numeric predicate/aggregate
+    queries with the streaming query kernel."""
+
+    def __init__(self, lib, handle):
+        self._lib = lib
+        self._h = handle
+
+    def _check(self, rc, what):
+        if rc:
+            err = GpuScanError(
+                f"{what} rc={rc}: {self._lib.yb_gpu_last_error().decode()}")
+            err.code = rc
+            raise err
+
+    def info(self):
+        out = y.SnapshotInfo()
+        self._check(self._lib.yb_gpu_snapshot_info(self._h, C.byref(out)),
+                    "snapshot_info")
+        return out
+
+    def query(self, preds, aggs):
+        """Run one query; returns a ScanResult. Unsupported queries raise
+        GpuScanError with .code == 9 (nothing is launched)."""
+        q = y.snapshot_query(preds, aggs)
+        res = y.ScanResult()
+        self._check(
+            self._lib.yb_gpu_snapshot_query(self._h, C.byref(q),
+                                            C.byref(res)), "snapshot_query")
+        return res
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        self._check(self._lib.yb_gpu_snapshot_kernel_ms(self._h,
+                                                        C.byref(ms)),
+                    "snapshot_kernel_ms")
+        return ms.value
+
+    def close(self):
+        if self._h:
+            self._lib.yb_gpu_snapshot_close(self._h)
             self._h = None

@@ -354,6 +354,94 @@ int yb_gpu_scan_kernel_ms(ybg_scan_t *s, double *total_ms, double *decode_ms);
 
 int yb_gpu_scan_close(ybg_scan_t *s);
 
+/* Returns 1 if the last yb_gpu_scan_execute on this handle was answered from
+ * a columnar snapshot (YBG_STAGE=1 transparent mode, below), 0 if it ran the
+ * block-bytes path. */
+int yb_gpu_scan_staged(ybg_scan_t *s);
+
+/* ---- columnar snapshot ---------------------------------------------------
+ *
+ * A DIFFERENT STORAGE CONTRACT from the rest of this header: everything
+ * above scans the reference's SST block bytes as they are; a snapshot is
+ * "rows visible at one read time, staged once, queried many times" — the
+ * role a read-point-pinned scan over an immutable tablet plays in the
+ * reference (one DocRowwiseIterator per statement at a fixed
+ * ReadHybridTime, doc_rowwise_iterator.cc:165-231; many statements of one
+ * transaction share the read point). It is an additional mode: the
+ * block-bytes path stays the default.
+ *
+ * Staged: every non-STRING value column and every non-STRING key column
+ * (key columns indexed like ybg_row_batch_t.key_datums), one 8-byte datum
+ * per row per column in the bit pattern yb_gpu_scan_next_batch delivers,
+ * plus one uint32 null mask per row (ybg_row_batch_t.null_masks layout).
+ * String columns are not staged. Rows are held in tablet key order.
+ *
+ *   yb_gpu_snapshot_build ~ DocRowwiseIterator ctor/Init + the full
+ *                           FetchNext loop at the read point, with its
+ *                           output kept resident instead of streamed
+ *   yb_gpu_snapshot_query ~ PgsqlReadOperation::ExecuteScalar row loop +
+ *                           EvalAggregate (pgsql_operation.cc:2808-2931,
+ *                           3171-3186) over the staged rows
+ */
+typedef struct ybg_snapshot ybg_snapshot_t;
+
+/* Build from a FED handle. Contents: every row visible at s->spec.read_time
+ * inside s->spec's DocKey bounds. The spec's predicates, aggregates,
+ * row_limit, group_col, emit_rows and backward are IGNORED for the build.
+ * The snapshot owns its memory and stays valid after yb_gpu_scan_close(s).
+ * Feed-time block pruning by the DocKey bounds is consistent with that (the
+ * bounds stay part of the snapshot). A handle whose feed pruned blocks by
+ * a leading-range-key IN / IN_RANGE predicate (yb_gpu_scan_feed_blocks on
+ * a range-sharded table) no longer holds every row inside the bounds: the
+ * build refuses it with error 9 — build from a handle opened without that
+ * predicate. (The YBG_STAGE=1 mode below still stages such a handle: there
+ * every query is the handle's own spec, predicate included.)
+ * Errors: 4 not fed, 6 corrupt entries, 8 row capacity, 9 option-pruned
+ * handle, 10 device. */
+int yb_gpu_snapshot_build(ybg_scan_t *s, ybg_snapshot_t **out);
+
+typedef struct {
+  uint64_t n_rows;          /* visible rows staged */
+  uint64_t entries_seen;    /* KV entries the build scan decoded */
+  uint64_t device_bytes;    /* HBM held by the snapshot */
+  double   build_ms;        /* device time of the build (events) */
+  uint32_t staged_value_cols; /* bit i: value col i staged (numeric) */
+  uint32_t nullable_cols;   /* bit i: value col i has >=1 NULL in the snapshot */
+  uint8_t  restart_ht[YBG_MAX_HT]; uint32_t restart_ht_len; /* as ybg_scan_result_t */
+} ybg_snapshot_info_t;
+int yb_gpu_snapshot_info(ybg_snapshot_t *sn, ybg_snapshot_info_t *out);
+
+typedef struct {
+  int32_t num_preds; ybg_pred_t preds[YBG_MAX_PREDS];
+  int32_t num_aggs;  ybg_agg_t  aggs[YBG_MAX_AGGS];
+} ybg_snapshot_query_t;
+
+/* Synchronous. Fills rows_scanned (= n_rows), rows_matched, entries_seen
+ * (= the build's), aggs[], restart_ht (= the build's).
+ * Predicates: GT..NE, IN and IN_RANGE on any staged value or key column;
+ * aggregates: all eight ops on staged value columns. Anything else (string
+ * column, IN_TUPLE, column index out of range, num_preds/num_aggs over the
+ * caps) returns 9 with a message naming the offending predicate or
+ * aggregate, and launches nothing. NULL semantics are the scan path's: a
+ * predicate on a NULL operand fails; COUNT(col), SUM, MIN, MAX skip NULLs;
+ * an aggregate with no contribution reports is_null. Results — double SUM
+ * included — are bit-identical across repeated queries and across
+ * separately built snapshots of the same tablet. */
+int yb_gpu_snapshot_query(ybg_snapshot_t *sn, const ybg_snapshot_query_t *q,
+                          ybg_scan_result_t *out);
+/* Device time (events) of the last query: query kernel + final reduce. */
+int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t *sn, double *query_ms);
+int yb_gpu_snapshot_close(ybg_snapshot_t *sn);
+
+/* Transparent mode: with YBG_STAGE=1 in the environment (read at execute
+ * time), yb_gpu_scan_execute on a plain aggregate handle (no emit_rows,
+ * group_col or row_limit) whose predicates and aggregates a snapshot can
+ * answer builds a snapshot on the handle's first execute, keeps it on the
+ * handle, and answers that and later executes with the query kernel;
+ * yb_gpu_scan_aggregate returns the same contents as the block path and
+ * yb_gpu_scan_kernel_ms reports the query kernel's time. Ineligible handles
+ * silently take the block path; unset or 0 changes nothing. */
+
 /* Returns 1 if a gfx950-class HIP device is visible. */
 int yb_gpu_available(void);
 

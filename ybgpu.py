@@ -473,6 +473,90 @@ def sim_scan(spec, data, offsets, n_blocks):
     return res
 
 
+class SnapshotQuery(C.Structure):
+    """ybg_snapshot_query_t."""
+    _fields_ = [("num_preds", C.c_int32), ("preds", Pred * MAX_PREDS),
+                ("num_aggs", C.c_int32), ("aggs", Agg * MAX_AGGS)]
+
+
+class SnapshotInfo(C.Structure):
+    """ybg_snapshot_info_t."""
+    _fields_ = [("n_rows", C.c_uint64), ("entries_seen", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("build_ms", C.c_double),
+                ("staged_value_cols", C.c_uint32),
+                ("nullable_cols", C.c_uint32),
+                ("restart_ht", C.c_uint8 * MAX_HT),
+                ("restart_ht_len", C.c_uint32)]
+
+
+def snapshot_query(preds, aggs):
+    """Pack predicate / aggregate lists into a SnapshotQuery. Counts over
+    the ABI caps are passed through (the ABI answers them with code 9); only
+    the first MAX_PREDS / MAX_AGGS entries are copied."""
+    q = SnapshotQuery()
+    q.num_preds = len(preds)
+    for i, p in enumerate(preds[:MAX_PREDS]):
+        q.preds[i] = p
+    q.num_aggs = len(aggs)
+    for i, a in enumerate(aggs[:MAX_AGGS]):
+        q.aggs[i] = a
+    return q
+
+
+def stageable(schema, preds, aggs):
+    """Can a columnar snapshot answer this query? Mirrors the ABI's code-9
+    rule (yb_gpu_snapshot_query): GT..NE / IN / IN_RANGE predicates on
+    numeric value or key columns, aggregates on numeric value columns,
+    indices in range, counts within the caps."""
+    if len(preds) > MAX_PREDS or len(aggs) > MAX_AGGS:
+        return False
+    nk = schema.num_hash_cols + schema.num_range_cols
+    for p in preds:
+        if p.op == PRED_IN_TUPLE or not PRED_GT <= p.op <= PRED_IN_RANGE:
+            return False
+        if p.is_key_col:
+            if not 0 <= p.col < nk or schema.key_types[p.col] == KT_STRING:
+                return False
+        else:
+            if not 0 <= p.col < schema.num_value_cols:
+                return False
+            if schema.value_cols[p.col].dtype == T_STRING:
+                return False
+        if p.op == PRED_IN and (not p.bytes or p.bytes_len % 8):
+            return False
+        if p.op == PRED_IN_RANGE and (not p.bytes or not p.bytes_len
+                                      or p.bytes_len % 24):
+            return False
+    for a in aggs:
+        if not AGG_COUNT <= a.op <= AGG_MAX_DOUBLE:
+            return False
+        if a.op == AGG_COUNT_STAR:
+            continue
+        if not 0 <= a.col < schema.num_value_cols:
+            return False
+        if schema.value_cols[a.col].dtype == T_STRING:
+            return False
+    return True
+
+
+def sim_snapshot_query(spec, data, offsets, n_blocks, preds, aggs):
+    """Host SIMULATOR of the columnar snapshot (ybg_sim_snapshot_query) —
+    TEST INFRASTRUCTURE: builds the snapshot layout from the spec's read
+    time and bounds (its predicates/aggregates are ignored) and runs the
+    device row loop (snap_device.h) over it for (preds, aggs)."""
+    lib = product()
+    f = _sig(lib, "ybg_sim_snapshot_query", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(SnapshotQuery),
+              C.POINTER(ScanResult)])
+    q = snapshot_query(preds, aggs)
+    res = ScanResult()
+    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), C.byref(res))
+    if rc != 0:
+        raise RuntimeError(f"ybg_sim_snapshot_query failed rc={rc}")
+    return res
+
+
 def sim_scan_fast(spec, data, offsets, n_blocks):
     """Host simulator of the SPECIALIZED fast batch scanner
     (scan_batch_fast + general fallback per aborted batch) — TEST

@@ -601,7 +601,9 @@ struct Rdr {
 // Interval table construction
 // ---------------------------------------------------------------------------
 
-#ifndef YBG_HOST_SIM
+// (kernels with external linkage: a second device translation unit that
+// includes this header defines YBG_NO_FEED_KERNELS)
+#if !defined(YBG_HOST_SIM) && !defined(YBG_NO_FEED_KERNELS)
 __global__ void k_count_restarts(const uint8_t* __restrict__ data,
                                  const uint64_t* __restrict__ offsets,
                                  uint64_t n_blocks,
@@ -1090,7 +1092,7 @@ struct EmitCtx {
   uint64_t* datums;      // [row_cap * nc]; strings: (len<<40)|varlen offset
   uint32_t* null_masks;  // [row_cap]
   uint16_t* hashes;      // [row_cap] kUInt16Hash prefix (doc_key.h:54)
-  uint8_t* varlen;
+  uint8_t* varlen;       // nullptr: string datums are written as 0
   uint64_t varlen_cap;
   unsigned long long* row_counter;
   unsigned long long* varlen_counter;
@@ -2439,7 +2441,9 @@ DEV void emit_row(const DevSpec& sp, EmitCtx* ec, const RowCtxT<NA>& rc,
     uint64_t d = 0;
     uint32_t soff = 0, sl = 0;
     if (key_col_value(sp, rk, rk_len, c, &d, &soff, &sl)) {
-      if (sp.key_types[c] == YBG_KT_STRING) {
+      if (sp.key_types[c] == YBG_KT_STRING && !ec->varlen) {
+        d = 0;  // no varlen heap (columnar snapshot build): strings dropped
+      } else if (sp.key_types[c] == YBG_KT_STRING) {
         // unescape into the varlen heap ('\0\1' -> '\0',
         // doc_kv_util.h:101-167)
         unsigned long long off = atomicAdd(ec->varlen_counter, sl);
@@ -2464,7 +2468,9 @@ DEV void emit_row(const DevSpec& sp, EmitCtx* ec, const RowCtxT<NA>& rc,
     uint64_t d = 0;
     if (!((rc.emit_null >> c) & 1)) {
       d = rc.emit_datums[c];
-      if ((rc.emit_str >> c) & 1) {
+      if (((rc.emit_str >> c) & 1) && !ec->varlen) {
+        d = 0;
+      } else if ((rc.emit_str >> c) & 1) {
         uint32_t sl = rc.emit_lens[c];
         unsigned long long off = atomicAdd(ec->varlen_counter, sl);
         if (off + sl > ec->varlen_cap) {

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "scan_device.h"
+#include "snap_internal.h"
 #include "sst_internal.h"
 #include "bloom_filter.h"
 #include "snappy_dev.h"
@@ -834,10 +835,17 @@ namespace {
 
 thread_local std::string g_err;
 
-int set_err(int code, const std::string& msg) {
+}  // namespace
+
+// shared with the snapshot code (snap_gpu.hip) through snap_internal.h
+int ybgint::set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+
+namespace {
+
+using ybgint::set_err;
 
 #define HIP_TRY(x)                                                        \
   do {                                                                    \
@@ -889,6 +897,14 @@ struct ybg_scan {
   bool bloom_rejected = false;
   double last_total_ms = 0, last_decode_ms = 0;
   std::vector<uint8_t> aux_host;
+  // handle-owned copies of the caller's bound and option-list bytes:
+  // s->spec points into these, so the spec stays readable after open
+  // (snapshot builds and staged executes translate it again later)
+  std::vector<std::vector<uint8_t>> spec_bytes;
+  // feed dropped blocks because of a leading-key IN / IN_RANGE predicate
+  // (not only DocKey bounds): the fed set no longer holds every row inside
+  // the bounds
+  bool pruned_by_options = false;
   // emit (next_batch) buffers
   uint32_t* d_flags_all = nullptr;
   uint64_t emit_row_cap = 0;
@@ -913,6 +929,11 @@ struct ybg_scan {
   unsigned long long* d_gc_out = nullptr;
   uint8_t* d_gb_out = nullptr;
   unsigned long long* d_g_counters = nullptr;
+  // YBG_STAGE=1 transparent mode: columnar snapshot built on the first
+  // eligible execute and kept for the handle's lifetime
+  ybg_snapshot_t* stage_snap = nullptr;
+  bool stage_failed = false;  // the build failed once: stay on the block path
+  bool staged_last = false;   // last execute was answered from the snapshot
 };
 
 extern "C" {
@@ -989,6 +1010,18 @@ int yb_gpu_scan_open(const ybg_scan_spec_t* spec, ybg_scan_t** out) {
   }
   auto* s = new ybg_scan();
   s->spec = *spec;
+  {
+    auto own = [&](const uint8_t** p, uint64_t len) {
+      if (!*p || !len) return;
+      s->spec_bytes.emplace_back(*p, *p + len);
+      *p = s->spec_bytes.back().data();
+    };
+    s->spec_bytes.reserve(YBG_MAX_PREDS + 2);  // no reallocation below
+    own(&s->spec.lower_bound, s->spec.lower_bound_len);
+    own(&s->spec.upper_bound, s->spec.upper_bound_len);
+    for (int i = 0; i < s->spec.num_preds && i < YBG_MAX_PREDS; ++i)
+      own(&s->spec.preds[i].bytes, s->spec.preds[i].bytes_len);
+  }
   s->aux_host.resize(1 << 20);
   uint32_t aux_len = 0;
   build_dev_spec(spec, &s->dspec, s->aux_host.data(), &aux_len,
@@ -1099,7 +1132,9 @@ size_t dockey_full_len(const uint8_t* k, size_t len) {
 bool compute_block_selection(const ybg_scan_spec_t& spec,
                              const uint8_t* blocks, const uint64_t* offsets,
                              uint64_t n_blocks,
-                             std::vector<uint8_t>* keep) {
+                             std::vector<uint8_t>* keep,
+                             bool* by_options = nullptr) {
+  if (by_options) *by_options = false;
   std::vector<KeyRange> allowed;
   KeyRange bounds;
   bool have_bounds = false;
@@ -1203,6 +1238,8 @@ bool compute_block_selection(const ybg_scan_spec_t& spec,
     (*keep)[b] = hit ? 1 : 0;
     if (!hit) any_skip = true;
   }
+  // option ranges (not only the DocKey bounds) shaped the selection
+  if (by_options) *by_options = any_skip && !opts.empty();
   return any_skip;
 }
 
@@ -1266,8 +1303,10 @@ int yb_gpu_scan_feed_blocks(ybg_scan_t* s, const uint8_t* blocks,
   if (const char* e = getenv("YBG_NOPRUNE")) noprune = atoi(e) != 0;
   if (!device && n_blocks && !noprune) {
     std::vector<uint8_t> keep;
+    bool by_options = false;
     if (compute_block_selection(s->spec, blocks, offsets, n_blocks,
-                                &keep)) {
+                                &keep, &by_options)) {
+      s->pruned_by_options = by_options;
       pruned_off.push_back(0);
       for (uint64_t b = 0; b < n_blocks; ++b) {
         if (!keep[b]) continue;
@@ -1554,12 +1593,153 @@ int yb_gpu_scan_feed_sst(ybg_scan_t* s, const uint8_t* file, uint64_t size,
   return 0;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------
+// Device part of row materialization (declared in snap_internal.h): the
+// flags pre-pass and the emit pass, parameterized on the DevSpec and the
+// EmitCtx so yb_gpu_scan_next_batch and the columnar-snapshot build share
+// one decoder.
+// ---------------------------------------------------------------------
+namespace ybgint {
+
+ScanView scan_view(ybg_scan_t* s) {
+  ScanView v;
+  v.spec = &s->spec;
+  v.stream = s->stream;
+  v.n_ivs = s->n_ivs;
+  v.fed = s->d_data != nullptr;
+  v.bloom_rejected = s->bloom_rejected;
+  v.pruned_by_options = s->pruned_by_options;
+  return v;
+}
+
+int scan_flags_pass(ybg_scan_t* s, const DevSpec& d, const uint8_t* d_aux) {
+  if (!s->d_flags_all)
+    HIP_TRY(hipMalloc(&s->d_flags_all, s->n_ivs * sizeof(uint32_t)));
+  HIP_TRY(hipMemsetAsync(s->d_flags_all, 0, s->n_ivs * sizeof(uint32_t),
+                         s->stream));
+  // flags pre-pass: resolves head-row ownership for EVERY interval
+  // (iv_flags written inside the walk; the bheads/walked side effects of
+  // this pass are only folded by scan_flags_stats)
+  HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_spec), &d, sizeof(DevSpec), 0,
+                                 hipMemcpyHostToDevice, s->stream));
+  auto flags_kernel = k_scan<2, 3>;
+  hipLaunchKernelGGL(flags_kernel, dim3(s->grid), dim3(kThreads), 0,
+                     s->stream, s->d_data, s->d_offsets, s->d_ivs,
+                     s->n_ivs, d_aux, s->d_rk_save, s->d_partials,
+                     s->d_heads, s->d_walked, s->d_flags_all, 1, s->ivb,
+                     s->n_batches, (const uint64_t*)nullptr,
+                     (const uint64_t*)nullptr,
+                     (const unsigned long long*)nullptr);
+  return 0;
+}
+
+int scan_flags_stats(ybg_scan_t* s, const DevSpec& d, ScanStats* out) {
+  // the flags pass is a k_scan<2,3> dispatch over fixed-ivb batches: head
+  // record stride 2*2+2, main partials half only. Folded with the
+  // aggregate slots off; the result record is a temporary so the handle's
+  // last aggregate result stays intact.
+  DevSpec rsp = d;
+  rsp.num_aggs = 0;
+  DevResult* d_res = nullptr;
+  HIP_TRY(hipMalloc(&d_res, sizeof(DevResult)));
+  hipLaunchKernelGGL(k_reduce_pre, dim3(1024), dim3(256), 0, s->stream, rsp,
+                     s->d_partials, s->n_partials, s->d_heads, s->d_walked,
+                     s->n_batches, 6, s->d_chunk);
+  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, s->stream, rsp,
+                     s->d_chunk, 1024, s->d_heads, s->d_cont, 0, d_res);
+  DevResult r;
+  hipError_t e = hipMemcpyAsync(&r, d_res, sizeof(r), hipMemcpyDeviceToHost,
+                                s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  HIP_WARN(hipFree(d_res));
+  if (e != hipSuccess) return set_err(10, hipGetErrorString(e));
+  memset(out, 0, sizeof(*out));
+  out->entries = r.entries;
+  out->scanned = r.scanned;
+  out->errs = r.errs;
+  uint32_t n = (uint32_t)r.restart_len;
+  if (n > YBG_MAX_HT) n = YBG_MAX_HT;
+  for (uint32_t i = 0; i < n; ++i)
+    out->restart_ht[i] = (uint8_t)(
+        (i < 8 ? r.restart_hi >> (56 - 8 * i)
+               : r.restart_lo >> (56 - 8 * (i - 8))) & 0xff);
+  out->restart_len = n;
+  return 0;
+}
+
+int scan_emit_pass(ybg_scan_t* s, const uint8_t* d_aux, EmitCtx ec,
+                   unsigned long long* d_counters,
+                   unsigned long long ctr[4]) {
+  HIP_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned long long),
+                         s->stream));
+  ec.row_counter = d_counters + 0;
+  ec.varlen_counter = d_counters + 1;
+  ec.overflow = d_counters + 2;
+  ec.head_consumed = s->d_flags_all;
+  int egrid = (int)std::min<uint64_t>(
+      (s->n_ivs + kEmitThreads - 1) / kEmitThreads, 8192);
+  // emit threads use their own rk_save area sized for the emit grid
+  uint64_t need_rk = (uint64_t)egrid * kEmitThreads * kKeyCap;
+  uint64_t have_rk = (uint64_t)s->grid * kThreads * kKeyCap;
+  uint8_t* rk_area = s->d_rk_save;
+  uint8_t* rk_extra = nullptr;
+  if (need_rk > have_rk) {
+    HIP_TRY(hipMalloc(&rk_extra, need_rk));
+    rk_area = rk_extra;
+  }
+  int nc_pad = ec.nc > 0 ? ec.nc : 1;
+  size_t emit_dyn_bytes =
+      (size_t)kEmitThreads * nc_pad * (sizeof(uint64_t) + sizeof(uint32_t));
+  hipLaunchKernelGGL(k_emit, dim3(egrid), dim3(kEmitThreads),
+                     emit_dyn_bytes, s->stream, s->d_data, s->d_offsets,
+                     s->d_ivs, s->n_ivs, d_aux, rk_area, ec, d_counters + 3,
+                     nc_pad);
+  hipError_t e = hipMemcpyAsync(ctr, d_counters,
+                                4 * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (rk_extra) HIP_WARN(hipFree(rk_extra));
+  if (e != hipSuccess) return set_err(10, hipGetErrorString(e));
+  return 0;
+}
+
+}  // namespace ybgint
+
+extern "C" {
+
 int yb_gpu_scan_execute(ybg_scan_t* s) {
   if (s->bloom_rejected) {
     s->executed = true;
     return 0;
   }
   if (!s->d_data) return set_err(4, "feed_blocks not called");
+  // YBG_STAGE=1: a plain aggregate scan with stageable predicates and
+  // aggregates is answered from a columnar snapshot built on the first
+  // execute. Anything else — and a failed build — takes the block path.
+  s->staged_last = false;
+  {
+    const char* e = getenv("YBG_STAGE");
+    if (e && atoi(e) == 1 && !s->stage_failed && !s->spec.emit_rows &&
+        s->spec.group_col == 0 && s->spec.row_limit == 0 &&
+        ybgint::stage_eligible(s->spec)) {
+      // the query is always the handle's own spec, so a block set pruned
+      // by that spec's own option predicate still answers it exactly
+      if (!s->stage_snap &&
+          ybgint::snapshot_build(s, &s->stage_snap, true) != 0) {
+        s->stage_snap = nullptr;
+        s->stage_failed = true;
+      }
+      if (s->stage_snap) {
+        int rc = ybgint::stage_launch(s->stage_snap, s->spec);
+        if (rc) return rc;
+        s->staged_last = true;
+        s->executed = true;
+        return 0;
+      }
+    }
+  }
   // the retry half of the partials is only partially covered by the retry
   // launch (or not at all on the general dispatch): zero it so the fold
   // sees clean records
@@ -1684,6 +1864,13 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
 
 int yb_gpu_scan_wait(ybg_scan_t* s) {
   if (!s->executed) return set_err(5, "execute not called");
+  if (s->staged_last) {
+    double ms = 0;
+    int rc = ybgint::stage_finish(s->stage_snap, s->spec, nullptr, &ms);
+    if (rc) return rc;
+    s->last_decode_ms = s->last_total_ms = ms;
+    return 0;
+  }
   HIP_TRY(hipStreamSynchronize(s->stream));
   float ms1 = 0, ms2 = 0;
   HIP_TRY(hipEventElapsedTime(&ms1, s->ev_start, s->ev_mid));
@@ -1701,6 +1888,10 @@ int yb_gpu_scan_aggregate(ybg_scan_t* s, ybg_scan_result_t* out) {
   }
   int rc = yb_gpu_scan_wait(s);
   if (rc) return rc;
+  if (s->staged_last) {
+    double ms = 0;
+    return ybgint::stage_finish(s->stage_snap, s->spec, out, &ms);
+  }
   DevResult r;
   HIP_TRY(hipMemcpy(&r, s->d_result, sizeof(r), hipMemcpyDeviceToHost));
   if (r.errs) return set_err(6, "corrupt entries encountered during scan");
@@ -1745,11 +1936,10 @@ int yb_gpu_scan_next_batch(ybg_scan_t* s, ybg_row_batch_t* out) {
   if (!s->d_data) return set_err(4, "feed_blocks not called");
   int nk = s->spec.schema.num_hash_cols + s->spec.schema.num_range_cols;
   int nc = s->spec.schema.num_value_cols;
-  if (!s->d_flags_all) {
+  if (!s->d_em_sort) {
     s->emit_row_cap = std::min<uint64_t>(s->n_ivs * 16ull, 32ull << 20);
     s->em_varlen_cap =
         std::min<uint64_t>(s->total_bytes + (1ull << 20), 1ull << 30);
-    HIP_TRY(hipMalloc(&s->d_flags_all, s->n_ivs * sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&s->d_em_sort, s->emit_row_cap * 8));
     HIP_TRY(hipMalloc(&s->d_em_key, s->emit_row_cap * 8 * (nk ? nk : 1)));
     HIP_TRY(hipMalloc(&s->d_em_dat, s->emit_row_cap * 8 * (nc ? nc : 1)));
@@ -1758,24 +1948,6 @@ int yb_gpu_scan_next_batch(ybg_scan_t* s, ybg_row_batch_t* out) {
     HIP_TRY(hipMalloc(&s->d_em_varlen, s->em_varlen_cap));
     HIP_TRY(hipMalloc(&s->d_em_counters, 4 * sizeof(unsigned long long)));
   }
-  HIP_TRY(hipMemsetAsync(s->d_flags_all, 0, s->n_ivs * sizeof(uint32_t),
-                         s->stream));
-  HIP_TRY(hipMemsetAsync(s->d_em_counters, 0, 4 * sizeof(unsigned long long),
-                         s->stream));
-  // flags pre-pass: resolves head-row ownership for EVERY interval
-  // (iv_flags written inside the walk; the bheads/walked side effects of
-  // this pass are scratch — nothing folds them)
-  HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_spec), &s->dspec,
-                                 sizeof(DevSpec), 0, hipMemcpyHostToDevice,
-                                 s->stream));
-  auto flags_kernel = k_scan<2, 3>;
-  hipLaunchKernelGGL(flags_kernel, dim3(s->grid), dim3(kThreads), 0,
-                     s->stream, s->d_data, s->d_offsets, s->d_ivs,
-                     s->n_ivs, s->d_aux, s->d_rk_save, s->d_partials,
-                     s->d_heads, s->d_walked, s->d_flags_all, 1, s->ivb,
-                     s->n_batches, (const uint64_t*)nullptr,
-                     (const uint64_t*)nullptr,
-                     (const unsigned long long*)nullptr);
   EmitCtx ec;
   ec.sort_key = s->d_em_sort;
   ec.key_datums = s->d_em_key;
@@ -1784,37 +1956,14 @@ int yb_gpu_scan_next_batch(ybg_scan_t* s, ybg_row_batch_t* out) {
   ec.hashes = s->d_em_hash;
   ec.varlen = s->d_em_varlen;
   ec.varlen_cap = s->em_varlen_cap;
-  ec.row_counter = s->d_em_counters + 0;
-  ec.varlen_counter = s->d_em_counters + 1;
-  ec.overflow = s->d_em_counters + 2;
   ec.row_cap = s->emit_row_cap;
   ec.nk = nk;
   ec.nc = nc;
-  ec.head_consumed = s->d_flags_all;
-  int egrid = (int)std::min<uint64_t>(
-      (s->n_ivs + kEmitThreads - 1) / kEmitThreads, 8192);
-  // emit threads use their own rk_save area sized for the emit grid
-  uint64_t need_rk = (uint64_t)egrid * kEmitThreads * kKeyCap;
-  uint64_t have_rk = (uint64_t)s->grid * kThreads * kKeyCap;
-  uint8_t* rk_area = s->d_rk_save;
-  uint8_t* rk_extra = nullptr;
-  if (need_rk > have_rk) {
-    HIP_TRY(hipMalloc(&rk_extra, need_rk));
-    rk_area = rk_extra;
-  }
-  int nc_pad = nc > 0 ? nc : 1;
-  size_t emit_dyn_bytes =
-      (size_t)kEmitThreads * nc_pad * (sizeof(uint64_t) + sizeof(uint32_t));
-  hipLaunchKernelGGL(k_emit, dim3(egrid), dim3(kEmitThreads),
-                     emit_dyn_bytes, s->stream, s->d_data, s->d_offsets,
-                     s->d_ivs, s->n_ivs, s->d_aux, rk_area, ec,
-                     s->d_em_counters + 3, nc_pad);
   unsigned long long ctr[4];
-  HIP_TRY(hipMemcpyAsync(ctr, s->d_em_counters,
-                         4 * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (rk_extra) HIP_WARN(hipFree(rk_extra));
+  int rc = ybgint::scan_flags_pass(s, s->dspec, s->d_aux);
+  if (rc) return rc;
+  rc = ybgint::scan_emit_pass(s, s->d_aux, ec, s->d_em_counters, ctr);
+  if (rc) return rc;
   if (ctr[3]) return set_err(6, "corrupt entries encountered during scan");
   if (ctr[2]) return set_err(8, "row batch capacity exceeded");
   uint64_t n_rows = ctr[0];
@@ -1981,6 +2130,15 @@ int yb_gpu_scan_restart_data(ybg_scan_t* s, uint8_t* ht_out,
     *len_out = 0;
     return 0;
   }
+  if (s->staged_last) {  // the snapshot carries its build scan's data
+    ybg_scan_result_t res;
+    double ms = 0;
+    int rc = ybgint::stage_finish(s->stage_snap, s->spec, &res, &ms);
+    if (rc) return rc;
+    memcpy(ht_out, res.restart_ht, res.restart_ht_len);
+    *len_out = res.restart_ht_len;
+    return 0;
+  }
   HIP_TRY(hipStreamSynchronize(s->stream));
   DevResult r;
   HIP_TRY(hipMemcpy(&r, s->d_result, sizeof(r), hipMemcpyDeviceToHost));
@@ -2016,7 +2174,10 @@ int yb_gpu_scan_kernel_ms(ybg_scan_t* s, double* total_ms, double* decode_ms) {
   return 0;
 }
 
+int yb_gpu_scan_staged(ybg_scan_t* s) { return s->staged_last ? 1 : 0; }
+
 int yb_gpu_scan_close(ybg_scan_t* s) {
+  if (s->stage_snap) yb_gpu_snapshot_close(s->stage_snap);
   if (s->d_data_owned && s->d_data) HIP_WARN(hipFree(s->d_data));
   if (s->d_offsets) HIP_WARN(hipFree(s->d_offsets));
   if (s->d_ivs) HIP_WARN(hipFree(s->d_ivs));

@@ -10,7 +10,9 @@ extern "C" unsigned long long ybg_fast_abort_hist[32] = {0};
 #define YBG_HOST_SIM 1
 #define YBG_DEV_QUAL inline
 #include "scan_device.h"
+#include "snap_device.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -480,6 +482,113 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
     ++n;
   }
   *n_out = n;
+  return 0;
+}
+
+// Columnar-snapshot simulator: the build (block scan with predicates and
+// aggregates stripped -> rows ordered by sort_key -> dense padded column
+// arrays, exactly the device snapshot's layout) followed by the
+// snap_device.h row loop, sequentially. `query` is a ybg_snapshot_query_t.
+// Returns 9 for a query the ABI rejects (same translation code).
+int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
+                           const uint64_t* offsets, uint64_t n_blocks,
+                           const ybg_snapshot_query_t* query,
+                           ybg_scan_result_t* out) {
+  ybg_scan_spec_t bs = *spec;
+  bs.num_preds = 0;
+  bs.num_aggs = 0;
+  bs.emit_rows = 0;
+  bs.row_limit = 0;
+  bs.group_col = 0;
+  bs.backward = 0;
+  // scan statistics + exact visible-row count (the build's flags pass)
+  ybg_scan_result_t stats;
+  int rc = ybg_sim_scan(&bs, data, offsets, n_blocks, &stats);
+  if (rc) return rc;
+  const ybg_schema_t& sc = spec->schema;
+  const int nk = sc.num_hash_cols + sc.num_range_cols;
+  const int nc = sc.num_value_cols;
+  const uint64_t cap = stats.rows_scanned ? stats.rows_scanned : 1;
+  std::vector<uint64_t> sort_key(cap), key_aos(cap * (nk ? nk : 1)),
+      dat_aos(cap * (nc ? nc : 1));
+  std::vector<uint32_t> null_aos(cap);
+  uint64_t n = 0, vl = 0;
+  // varlen heap absent: string datums are dropped, as in the device build
+  rc = ybg_sim_emit(&bs, data, offsets, n_blocks, cap, sort_key.data(),
+                    key_aos.data(), dat_aos.data(), null_aos.data(), nullptr,
+                    0, &n, &vl);
+  if (rc) return rc;
+  if (n != stats.rows_scanned) return 8;
+
+  std::vector<uint32_t> perm(n);
+  for (uint64_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+  std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+    return sort_key[a] < sort_key[b];
+  });
+  const uint64_t padded = snap_padded_rows(n);
+  std::vector<std::vector<uint64_t>> val(nc), key(nk);
+  std::vector<uint32_t> nullmask(padded, 0);
+  SnapCols cols;
+  memset(&cols, 0, sizeof(cols));
+  for (int c = 0; c < nc; ++c) {
+    if (sc.value_cols[c].dtype == YBG_T_STRING) continue;
+    val[c].assign(padded, 0);
+    for (uint64_t r = 0; r < n; ++r)
+      val[c][r] = dat_aos[(uint64_t)perm[r] * nc + c];
+    cols.val[c] = val[c].data();
+  }
+  for (int c = 0; c < nk; ++c) {
+    if (sc.key_types[c] == YBG_KT_STRING) continue;
+    key[c].assign(padded, 0);
+    for (uint64_t r = 0; r < n; ++r)
+      key[c][r] = key_aos[(uint64_t)perm[r] * nk + c];
+    cols.key[c] = key[c].data();
+  }
+  const uint32_t nc_mask = nc >= 32 ? 0xffffffffu : ((1u << nc) - 1u);
+  for (uint64_t r = 0; r < n; ++r) {
+    nullmask[r] = null_aos[perm[r]];
+    cols.nullable_cols |= nullmask[r] & nc_mask;
+  }
+  cols.nullmask = nullmask.data();
+
+  SnapQuery q;
+  std::vector<uint8_t> aux;
+  char err[192];
+  rc = snap_build_query(sc, &cols, query->num_preds, query->preds,
+                        query->num_aggs, query->aggs, n, &aux, &q, err,
+                        sizeof(err));
+  if (rc) return rc;
+  q.aux = aux.data();
+  SnapResult res;
+  memset(&res, 0, sizeof(res));
+  // row pairs in ascending order, as one device lane walks them; the
+  // null-mask variant is chosen like the kernel dispatch chooses it
+  const uint64_t n_pairs = (n + kSnapVec - 1) / kSnapVec;
+  auto run = [&](auto nulls_tag, auto gen_tag) {
+    constexpr bool NULLS = decltype(nulls_tag)::value;
+    constexpr bool GEN = decltype(gen_tag)::value;
+    for (uint64_t pi = 0; pi < n_pairs; ++pi) {
+      for (int k = 0; k < kSnapVec; ++k) {
+        const uint64_t r = pi * kSnapVec + k;
+        uint64_t pv[YBG_MAX_PREDS] = {0}, av[YBG_MAX_AGGS] = {0};
+        for (int i = 0; i < q.num_preds; ++i) pv[i] = q.preds[i].col[r];
+        for (int g = 0; g < q.num_aggs; ++g)
+          if (q.aggs[g].col) av[g] = q.aggs[g].col[r];
+        snap_row<YBG_MAX_PREDS, YBG_MAX_AGGS, NULLS, GEN>(
+            q, pv, av, NULLS ? q.nullmask[r] : 0u, r < n, &res.matched,
+            res.agg_val, res.agg_cnt);
+      }
+    }
+  };
+  if (q.any_nullable) {
+    if (q.general) run(std::true_type{}, std::true_type{});
+    else run(std::true_type{}, std::false_type{});
+  } else {
+    if (q.general) run(std::false_type{}, std::true_type{});
+    else run(std::false_type{}, std::false_type{});
+  }
+  snap_fill_result(res, n, stats.entries_seen, stats.restart_ht,
+                   stats.restart_ht_len, query->num_aggs, query->aggs, out);
   return 0;
 }
 

@@ -1,0 +1,657 @@
+// yugabyte-db_amd/csrc/snap_gpu.hip — columnar snapshot: build (sort +
+// transpose of the block scan's materialized rows) and the dense streaming
+// query kernel for CDNA4 (gfx950).
+//
+// Storage contract: NOT "scan the reference's SST block
+// bytes" but "rows visible at one read time, staged once". The build
+// reuses the block path's decode + MVCC resolution (scan_flags_pass /
+// scan_emit_pass, scan_gpu.hip) with predicates and aggregates stripped,
+// orders the rows by tablet position and gathers every numeric value/key
+// column into its own dense array plus one null-mask word per row. Queries
+// then stream only the columns they reference:
+//  * k_snap_query: 256-thread workgroups, each lane owns contiguous row
+//    PAIRS so every column access is one 16-byte load; all loads of an
+//    iteration are issued before the first compare; predicates fold
+//    branch-free into a pass bit; lanes fold rows in ascending order, waves
+//    fold lanes in fixed order.
+//  * k_snap_reduce: one workgroup folds the wave partials in fixed order.
+//  The grid is a pure function of n_rows, so together with the sorted
+//  build, results (double SUM included) are bit-identical across queries
+//  and across separately built snapshots of the same tablet.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define YBG_NO_FEED_KERNELS 1  // scan_gpu.hip owns the feed kernels
+#include "snap_device.h"
+#include "snap_internal.h"
+
+using namespace ybgdev;
+using ybgint::set_err;
+
+namespace {
+
+#define HIP_TRY(x)                                                        \
+  do {                                                                    \
+    hipError_t _e = (x);                                                  \
+    if (_e != hipSuccess)                                                 \
+      return set_err(10, std::string(#x) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+#define HIP_WARN(x) \
+  do { hipError_t _e = (x); (void)_e; } while (0)
+
+typedef unsigned long long snap_u64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int snap_u32x2 __attribute__((ext_vector_type(2)));
+
+// ---------------------------------------------------------------------------
+// Query kernel. NP / NA: compile-time caps of the unrolled predicate /
+// aggregate loops (slots past num_preds / num_aggs are skipped with uniform
+// branches and load nothing). NULLS = false never touches the null-mask
+// array. GEN routes compares through pred_compare (IN / IN_RANGE lists).
+// ---------------------------------------------------------------------------
+template <int NP, int NA, bool NULLS, bool GEN>
+__global__ __launch_bounds__(kSnapThreads) void k_snap_query(
+    SnapQuery q, uint64_t* __restrict__ partials) {
+  const uint64_t n_pairs = (q.n_rows + kSnapVec - 1) / kSnapVec;
+  const uint64_t span = (uint64_t)gridDim.x * kSnapThreads;
+  uint64_t matched = 0;
+  // constant-indexed only (every loop over them is unrolled), so they stay
+  // in registers
+  uint64_t agg_val[NA], agg_cnt[NA];
+#pragma unroll
+  for (int g = 0; g < NA; ++g) { agg_val[g] = 0; agg_cnt[g] = 0; }
+
+  for (uint64_t pi = (uint64_t)blockIdx.x * kSnapThreads + threadIdx.x;
+       pi < n_pairs; pi += span) {
+    const uint64_t r0 = pi * kSnapVec;
+    // all column loads of the iteration back to back, before any compare
+    snap_u64x2 pv[NP], av[NA];
+    snap_u32x2 nm = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      pv[i] = snap_u64x2{0ull, 0ull};
+      if (i < q.num_preds)
+        pv[i] = *reinterpret_cast<const snap_u64x2*>(q.preds[i].col + r0);
+    }
+#pragma unroll
+    for (int g = 0; g < NA; ++g) {
+      av[g] = snap_u64x2{0ull, 0ull};
+      if (g < q.num_aggs && q.aggs[g].col)
+        av[g] = *reinterpret_cast<const snap_u64x2*>(q.aggs[g].col + r0);
+    }
+    if (NULLS) nm = *reinterpret_cast<const snap_u32x2*>(q.nullmask + r0);
+
+    uint64_t p0[NP], p1[NP], a0[NA], a1[NA];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { p0[i] = pv[i].x; p1[i] = pv[i].y; }
+#pragma unroll
+    for (int g = 0; g < NA; ++g) { a0[g] = av[g].x; a1[g] = av[g].y; }
+    // ascending row order per lane; the odd tail's padding row is masked
+    snap_row<NP, NA, NULLS, GEN>(q, p0, a0, nm.x, true, &matched, agg_val,
+                                 agg_cnt);
+    snap_row<NP, NA, NULLS, GEN>(q, p1, a1, nm.y, r0 + 1 < q.n_rows,
+                                 &matched, agg_val, agg_cnt);
+  }
+
+  // wave fold in fixed lane order => deterministic (double SUM included)
+  const unsigned lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    matched += __shfl_down((unsigned long long)matched, off);
+  __shared__ uint64_t red_val[kSnapThreads], red_cnt[kSnapThreads];
+  const uint64_t wave_id =
+      ((uint64_t)blockIdx.x * kSnapThreads + threadIdx.x) >> 6;
+  uint64_t* out = partials + wave_id * kSnapPartialStride;
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    if (g >= q.num_aggs) continue;
+    red_val[threadIdx.x] = agg_val[g];
+    red_cnt[threadIdx.x] = agg_cnt[g];
+    __syncthreads();
+    if (lane == 0) {
+      uint64_t fv = 0, fc = 0;
+      for (int l = 0; l < 64; ++l)
+        combine1(q.aggs[g].op, &fv, &fc, red_val[threadIdx.x + l],
+                 red_cnt[threadIdx.x + l]);
+      out[1 + 2 * g] = fv;
+      out[2 + 2 * g] = fc;
+    }
+    __syncthreads();
+  }
+  if (lane == 0) out[0] = matched;
+}
+
+struct SnapOps {
+  int32_t num_aggs;
+  int32_t op[YBG_MAX_AGGS];
+};
+
+// One workgroup: thread t folds partials t, t+256, ... in ascending order,
+// thread 0 folds the 256 thread results in order.
+__global__ __launch_bounds__(256) void k_snap_reduce(
+    SnapOps ops, const uint64_t* __restrict__ partials, uint64_t n_partials,
+    SnapResult* __restrict__ out) {
+  __shared__ uint64_t sval[256], scnt[256];
+  const unsigned t = threadIdx.x;
+  {
+    uint64_t acc = 0;
+    for (uint64_t i = t; i < n_partials; i += 256)
+      acc += partials[i * kSnapPartialStride];
+    sval[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+      uint64_t total = 0;
+      for (int i = 0; i < 256; ++i) total += sval[i];
+      out->matched = total;
+    }
+    __syncthreads();
+  }
+  for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+    uint64_t av = 0, ac = 0;
+    if (g < ops.num_aggs) {
+      for (uint64_t i = t; i < n_partials; i += 256)
+        combine1(ops.op[g], &av, &ac,
+                 partials[i * kSnapPartialStride + 1 + 2 * g],
+                 partials[i * kSnapPartialStride + 2 + 2 * g]);
+    }
+    sval[t] = av;
+    scnt[t] = ac;
+    __syncthreads();
+    if (t == 0) {
+      uint64_t fv = 0, fc = 0;
+      if (g < ops.num_aggs)
+        for (int i = 0; i < 256; ++i)
+          combine1(ops.op[g], &fv, &fc, sval[i], scnt[i]);
+      out->agg_val[g] = fv;
+      out->agg_cnt[g] = fc;
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Build kernels
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_snap_iota(uint32_t* __restrict__ v,
+                                                   uint64_t n) {
+  uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) v[i] = (uint32_t)i;
+}
+
+struct SnapXpose {
+  const uint64_t* key_aos;   // [rows * nk]
+  const uint64_t* dat_aos;   // [rows * nc]
+  const uint32_t* null_aos;  // [rows]
+  int32_t nk, nc;
+  uint64_t* val[YBG_MAX_COLS];    // nullptr: column not staged
+  uint64_t* key[YBG_MAX_KEYCOLS];
+  uint32_t* nullmask;
+  uint32_t nc_mask;  // bits of real value columns
+};
+
+// Gather: output row r takes emit slot perm[r] (perm = slots ordered by
+// sort_key), each staged column into its own dense array. The rows' null
+// masks are OR-ed into *nullable_out with one atomic per wave.
+__global__ __launch_bounds__(256) void k_snap_transpose(
+    SnapXpose x, const uint32_t* __restrict__ perm, uint64_t n_rows,
+    uint32_t* __restrict__ nullable_out) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t nm = 0;
+  if (r < n_rows) {
+    const uint64_t slot = perm[r];
+    for (int c = 0; c < x.nc; ++c)
+      if (x.val[c]) x.val[c][r] = x.dat_aos[slot * x.nc + c];
+    for (int c = 0; c < x.nk; ++c)
+      if (x.key[c]) x.key[c][r] = x.key_aos[slot * x.nk + c];
+    nm = x.null_aos[slot];
+    x.nullmask[r] = nm;
+    nm &= x.nc_mask;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nm |= __shfl_xor(nm, off);
+  if ((threadIdx.x & 63) == 0 && nm) atomicOr(nullable_out, nm);
+}
+
+// temporaries of one build: freed on every exit path
+struct DevTmp {
+  std::vector<void*> ptrs;
+  ~DevTmp() { release(); }
+  void release() {
+    for (void* p : ptrs) HIP_WARN(hipFree(p));
+    ptrs.clear();
+  }
+  template <class T>
+  hipError_t alloc(T** out, size_t bytes) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e == hipSuccess) ptrs.push_back(p);
+    *out = (T*)p;
+    return e;
+  }
+};
+
+}  // namespace
+
+struct ybg_snapshot {
+  ybg_schema_t schema;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+  uint64_t n_rows = 0;
+  uint64_t entries_seen = 0;
+  uint64_t device_bytes = 0;
+  double build_ms = 0, last_query_ms = 0;
+  uint32_t staged_value_cols = 0, staged_key_cols = 0, nullable_cols = 0;
+  uint8_t restart_ht[YBG_MAX_HT] = {0};
+  uint32_t restart_len = 0;
+  uint64_t* d_val[YBG_MAX_COLS] = {nullptr};
+  uint64_t* d_key[YBG_MAX_KEYCOLS] = {nullptr};
+  uint32_t* d_nullmask = nullptr;
+  uint64_t* d_partials = nullptr;  // [snap_grid * 4 waves] wave partials
+  SnapResult* d_result = nullptr;
+  uint8_t* d_aux = nullptr;        // IN / IN_RANGE lists of the last query
+  size_t aux_cap = 0;
+  std::vector<uint8_t> aux_host;
+  bool pending = false;            // a launched query awaits its fetch
+  bool timed = false;              // that query recorded events
+  SnapResult h_result;
+};
+
+namespace {
+
+void snap_free(ybg_snapshot* sn) {
+  for (int c = 0; c < YBG_MAX_COLS; ++c)
+    if (sn->d_val[c]) HIP_WARN(hipFree(sn->d_val[c]));
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c)
+    if (sn->d_key[c]) HIP_WARN(hipFree(sn->d_key[c]));
+  if (sn->d_nullmask) HIP_WARN(hipFree(sn->d_nullmask));
+  if (sn->d_partials) HIP_WARN(hipFree(sn->d_partials));
+  if (sn->d_result) HIP_WARN(hipFree(sn->d_result));
+  if (sn->d_aux) HIP_WARN(hipFree(sn->d_aux));
+  if (sn->ev_q0) HIP_WARN(hipEventDestroy(sn->ev_q0));
+  if (sn->ev_q1) HIP_WARN(hipEventDestroy(sn->ev_q1));
+  if (sn->stream) HIP_WARN(hipStreamDestroy(sn->stream));
+  delete sn;
+}
+
+template <int NP, int NA>
+void snap_launch_fast(const SnapQuery& q, int grid, hipStream_t st,
+                      uint64_t* partials) {
+  if (q.any_nullable)
+    hipLaunchKernelGGL((k_snap_query<NP, NA, true, false>), dim3(grid),
+                       dim3(kSnapThreads), 0, st, q, partials);
+  else
+    hipLaunchKernelGGL((k_snap_query<NP, NA, false, false>), dim3(grid),
+                       dim3(kSnapThreads), 0, st, q, partials);
+}
+
+// Translate + launch (async on the snapshot's stream). Error 9 launches
+// nothing and leaves the snapshot usable.
+int snap_launch(ybg_snapshot* sn, int32_t num_preds, const ybg_pred_t* preds,
+                int32_t num_aggs, const ybg_agg_t* aggs) {
+  SnapCols cols;
+  memset(&cols, 0, sizeof(cols));
+  for (int c = 0; c < YBG_MAX_COLS; ++c) cols.val[c] = sn->d_val[c];
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c) cols.key[c] = sn->d_key[c];
+  cols.nullmask = sn->d_nullmask;
+  cols.nullable_cols = sn->nullable_cols;
+  SnapQuery q;
+  char err[192];
+  // the previous query's lists may still be in flight from aux_host
+  if (sn->pending) HIP_TRY(hipStreamSynchronize(sn->stream));
+  sn->pending = false;
+  sn->aux_host.clear();
+  int rc = snap_build_query(sn->schema, &cols, num_preds, preds, num_aggs,
+                            aggs, sn->n_rows, &sn->aux_host, &q, err,
+                            sizeof(err));
+  if (rc) return set_err(rc, err);
+  sn->timed = false;
+  if (sn->n_rows == 0) {
+    // empty snapshot: zero counts, every aggregate NULL; nothing launched
+    memset(&sn->h_result, 0, sizeof(sn->h_result));
+    sn->last_query_ms = 0;
+    sn->pending = true;
+    return 0;
+  }
+  if (q.general) {
+    if (sn->aux_host.size() > sn->aux_cap) {
+      if (sn->d_aux) HIP_WARN(hipFree(sn->d_aux));
+      sn->d_aux = nullptr;
+      sn->aux_cap = 0;
+      HIP_TRY(hipMalloc(&sn->d_aux, sn->aux_host.size()));
+      sn->aux_cap = sn->aux_host.size();
+    }
+    HIP_TRY(hipMemcpyAsync(sn->d_aux, sn->aux_host.data(),
+                           sn->aux_host.size(), hipMemcpyHostToDevice,
+                           sn->stream));
+    q.aux = sn->d_aux;
+  }
+  const int grid = (int)snap_grid(sn->n_rows);
+  HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+  if (q.general) {
+    if (q.any_nullable)
+      hipLaunchKernelGGL((k_snap_query<8, 8, true, true>), dim3(grid),
+                         dim3(kSnapThreads), 0, sn->stream, q,
+                         sn->d_partials);
+    else
+      hipLaunchKernelGGL((k_snap_query<8, 8, false, true>), dim3(grid),
+                         dim3(kSnapThreads), 0, sn->stream, q,
+                         sn->d_partials);
+  } else {
+    const int np = q.num_preds <= 4 ? 4 : 8;
+    const int na = q.num_aggs <= 2 ? 2 : (q.num_aggs <= 4 ? 4 : 8);
+    switch (np * 10 + na) {
+      case 42: snap_launch_fast<4, 2>(q, grid, sn->stream, sn->d_partials);
+        break;
+      case 44: snap_launch_fast<4, 4>(q, grid, sn->stream, sn->d_partials);
+        break;
+      case 48: snap_launch_fast<4, 8>(q, grid, sn->stream, sn->d_partials);
+        break;
+      case 82: snap_launch_fast<8, 2>(q, grid, sn->stream, sn->d_partials);
+        break;
+      case 84: snap_launch_fast<8, 4>(q, grid, sn->stream, sn->d_partials);
+        break;
+      default: snap_launch_fast<8, 8>(q, grid, sn->stream, sn->d_partials);
+        break;
+    }
+  }
+  SnapOps ops;
+  memset(&ops, 0, sizeof(ops));
+  ops.num_aggs = q.num_aggs;
+  for (int g = 0; g < q.num_aggs; ++g) ops.op[g] = q.aggs[g].op;
+  hipLaunchKernelGGL(k_snap_reduce, dim3(1), dim3(256), 0, sn->stream, ops,
+                     sn->d_partials,
+                     (uint64_t)grid * (kSnapThreads / 64), sn->d_result);
+  HIP_TRY(hipEventRecord(sn->ev_q1, sn->stream));
+  HIP_TRY(hipMemcpyAsync(&sn->h_result, sn->d_result, sizeof(SnapResult),
+                         hipMemcpyDeviceToHost, sn->stream));
+  sn->pending = true;
+  sn->timed = true;
+  return 0;
+}
+
+// Wait for the launched query; out may be null (timing only).
+int snap_finish(ybg_snapshot* sn, int32_t num_aggs, const ybg_agg_t* aggs,
+                ybg_scan_result_t* out) {
+  if (!sn->pending) return set_err(5, "snapshot query not launched");
+  if (sn->timed) {
+    HIP_TRY(hipStreamSynchronize(sn->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, sn->ev_q0, sn->ev_q1));
+    sn->last_query_ms = ms;
+    sn->timed = false;
+  }
+  if (out)
+    snap_fill_result(sn->h_result, sn->n_rows, sn->entries_seen,
+                     sn->restart_ht, sn->restart_len, num_aggs, aggs, out);
+  return 0;
+}
+
+}  // namespace
+
+namespace ybgint {
+
+bool stage_eligible(const ybg_scan_spec_t& spec) {
+  std::vector<uint8_t> aux;
+  SnapQuery q;
+  char err[192];
+  return snap_build_query(spec.schema, nullptr, spec.num_preds, spec.preds,
+                          spec.num_aggs, spec.aggs, 0, &aux, &q, err,
+                          sizeof(err)) == 0;
+}
+
+int stage_launch(ybg_snapshot_t* snap, const ybg_scan_spec_t& spec) {
+  return snap_launch(snap, spec.num_preds, spec.preds, spec.num_aggs,
+                     spec.aggs);
+}
+
+int stage_finish(ybg_snapshot_t* snap, const ybg_scan_spec_t& spec,
+                 ybg_scan_result_t* out, double* query_ms) {
+  int rc = snap_finish(snap, spec.num_aggs, spec.aggs, out);
+  if (rc) return rc;
+  *query_ms = snap->last_query_ms;
+  return 0;
+}
+
+}  // namespace ybgint
+
+int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
+                           bool allow_option_pruned) {
+  *out = nullptr;
+  ybgint::ScanView v = ybgint::scan_view(s);
+  if (!v.fed && !v.bloom_rejected)
+    return set_err(4, "feed_blocks not called");
+  // A snapshot promises every row inside the bounds, whatever the spec's
+  // predicates were. Feed-time pruning by DocKey bounds keeps that promise
+  // (the bounds stay part of the snapshot); pruning by a leading-key IN /
+  // IN_RANGE predicate does not.
+  if (v.pruned_by_options && !allow_option_pruned)
+    return set_err(9,
+                   "snapshot build: the handle's blocks were pruned at feed "
+                   "time by its leading-key IN/IN_RANGE predicate; build "
+                   "from a handle opened without that predicate");
+  const ybg_schema_t& sc = v.spec->schema;
+  const int nk = sc.num_hash_cols + sc.num_range_cols;
+  const int nc = sc.num_value_cols;
+
+  ybg_snapshot* sn = new ybg_snapshot();
+  sn->schema = sc;
+  for (int c = 0; c < nc; ++c)
+    if (sc.value_cols[c].dtype != YBG_T_STRING)
+      sn->staged_value_cols |= 1u << c;
+  for (int c = 0; c < nk; ++c)
+    if (sc.key_types[c] != YBG_KT_STRING) sn->staged_key_cols |= 1u << c;
+  // every exit below the allocations frees the half-built snapshot
+  struct Guard {
+    ybg_snapshot* sn;
+    ~Guard() { if (sn) snap_free(sn); }
+  } guard{sn};
+  HIP_TRY(hipStreamCreate(&sn->stream));
+  HIP_TRY(hipEventCreate(&sn->ev_q0));
+  HIP_TRY(hipEventCreate(&sn->ev_q1));
+  HIP_TRY(hipMalloc(&sn->d_result, sizeof(SnapResult)));
+  sn->device_bytes += sizeof(SnapResult);
+
+  if (!v.bloom_rejected) {
+    // the build spec: bounds and read time kept, everything else off
+    ybg_scan_spec_t bs = *v.spec;
+    bs.num_preds = 0;
+    bs.num_aggs = 0;
+    bs.emit_rows = 1;
+    bs.row_limit = 0;
+    bs.group_col = 0;
+    bs.backward = 0;
+    DevSpec d;
+    std::vector<uint8_t> aux(1 << 16);
+    uint32_t aux_len = 0;
+    build_dev_spec(&bs, &d, aux.data(), &aux_len, (uint32_t)aux.size());
+    aux.resize(aux_len + 16, 0);  // windowed-load tail slack (see open)
+
+    DevTmp tmp;
+    uint8_t* d_aux = nullptr;
+    HIP_TRY(tmp.alloc(&d_aux, aux.size()));
+    HIP_TRY(hipMemcpy(d_aux, aux.data(), aux.size(), hipMemcpyHostToDevice));
+    hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
+    HIP_TRY(hipEventCreate(&ev_b0));
+    HIP_TRY(hipEventCreate(&ev_b1));
+    struct EvGuard {
+      hipEvent_t a, b;
+      ~EvGuard() { HIP_WARN(hipEventDestroy(a)); HIP_WARN(hipEventDestroy(b)); }
+    } evg{ev_b0, ev_b1};
+    HIP_TRY(hipEventRecord(ev_b0, v.stream));
+
+    // pass 1: head-row ownership + the scan statistics. The visible-row
+    // count sizes the temporaries exactly (no fixed row cap).
+    int rc = ybgint::scan_flags_pass(s, d, d_aux);
+    if (rc) return rc;
+    ybgint::ScanStats st;
+    rc = ybgint::scan_flags_stats(s, d, &st);
+    if (rc) return rc;
+    if (st.errs) return set_err(6, "corrupt entries encountered during scan");
+    if (st.scanned >= (1ull << 32))
+      return set_err(8, "snapshot row capacity (2^32 - 1) exceeded");
+    const uint64_t n = st.scanned;
+    sn->n_rows = n;
+    sn->entries_seen = st.entries;
+    memcpy(sn->restart_ht, st.restart_ht, st.restart_len);
+    sn->restart_len = st.restart_len;
+
+    if (n) {
+      // pass 2: materialize into snapshot-owned AoS temporaries
+      uint64_t *t_sort = nullptr, *t_key = nullptr, *t_dat = nullptr;
+      uint32_t* t_null = nullptr;
+      uint16_t* t_hash = nullptr;
+      unsigned long long* t_ctr = nullptr;
+      HIP_TRY(tmp.alloc(&t_sort, n * 8));
+      HIP_TRY(tmp.alloc(&t_key, n * 8 * (nk ? nk : 1)));
+      HIP_TRY(tmp.alloc(&t_dat, n * 8 * (nc ? nc : 1)));
+      HIP_TRY(tmp.alloc(&t_null, n * 4));
+      HIP_TRY(tmp.alloc(&t_hash, n * 2));
+      HIP_TRY(tmp.alloc(&t_ctr, 4 * sizeof(unsigned long long)));
+      EmitCtx ec;
+      memset(&ec, 0, sizeof(ec));
+      ec.sort_key = t_sort;
+      ec.key_datums = t_key;
+      ec.datums = t_dat;
+      ec.null_masks = t_null;
+      ec.hashes = t_hash;
+      ec.varlen = nullptr;  // strings are not staged
+      ec.varlen_cap = 0;
+      ec.row_cap = n;
+      ec.nk = nk;
+      ec.nc = nc;
+      unsigned long long ctr[4];
+      rc = ybgint::scan_emit_pass(s, d_aux, ec, t_ctr, ctr);
+      if (rc) return rc;
+      if (ctr[3])
+        return set_err(6, "corrupt entries encountered during scan");
+      // invariant: k_emit materializes exactly the rows the flags pass
+      // counted as visible (same DevSpec, same ownership flags); the
+      // buffers hold n rows, so any disagreement surfaces here as error 8
+      if (ctr[2] || ctr[0] != n)
+        return set_err(8, "snapshot row capacity exceeded");
+
+      // order the emit slots by tablet position (k_emit appends in
+      // atomic-counter order, which differs run to run)
+      uint64_t* t_sorted = nullptr;
+      uint32_t *t_iota = nullptr, *t_perm = nullptr;
+      HIP_TRY(tmp.alloc(&t_sorted, n * 8));
+      HIP_TRY(tmp.alloc(&t_iota, n * 4));
+      HIP_TRY(tmp.alloc(&t_perm, n * 4));
+      const int rgrid = (int)((n + 255) / 256);
+      hipLaunchKernelGGL(k_snap_iota, dim3(rgrid), dim3(256), 0, v.stream,
+                         t_iota, n);
+      size_t sort_bytes = 0;
+      HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, t_sort, t_sorted,
+                                        t_iota, t_perm, (size_t)n, 0, 64,
+                                        v.stream));
+      void* t_sorttmp = nullptr;
+      HIP_TRY(tmp.alloc(&t_sorttmp, sort_bytes));
+      HIP_TRY(rocprim::radix_sort_pairs(t_sorttmp, sort_bytes, t_sort,
+                                        t_sorted, t_iota, t_perm, (size_t)n,
+                                        0, 64, v.stream));
+
+      // dense per-column arrays: one allocation each, padded to the query
+      // kernel's vector width plus a zeroed vector of slack
+      const uint64_t padded = snap_padded_rows(n);
+      SnapXpose x;
+      memset(&x, 0, sizeof(x));
+      x.key_aos = t_key;
+      x.dat_aos = t_dat;
+      x.null_aos = t_null;
+      x.nk = nk;
+      x.nc = nc;
+      x.nc_mask = nc >= 32 ? 0xffffffffu : ((1u << nc) - 1u);
+      for (int c = 0; c < nc; ++c) {
+        if (!((sn->staged_value_cols >> c) & 1)) continue;
+        HIP_TRY(hipMalloc(&sn->d_val[c], padded * 8));
+        sn->device_bytes += padded * 8;
+        HIP_TRY(hipMemsetAsync(sn->d_val[c] + n, 0, (padded - n) * 8,
+                               v.stream));
+        x.val[c] = sn->d_val[c];
+      }
+      for (int c = 0; c < nk; ++c) {
+        if (!((sn->staged_key_cols >> c) & 1)) continue;
+        HIP_TRY(hipMalloc(&sn->d_key[c], padded * 8));
+        sn->device_bytes += padded * 8;
+        HIP_TRY(hipMemsetAsync(sn->d_key[c] + n, 0, (padded - n) * 8,
+                               v.stream));
+        x.key[c] = sn->d_key[c];
+      }
+      HIP_TRY(hipMalloc(&sn->d_nullmask, padded * 4));
+      sn->device_bytes += padded * 4;
+      HIP_TRY(hipMemsetAsync(sn->d_nullmask + n, 0, (padded - n) * 4,
+                             v.stream));
+      x.nullmask = sn->d_nullmask;
+      uint32_t* t_nullable = nullptr;
+      HIP_TRY(tmp.alloc(&t_nullable, 4));
+      HIP_TRY(hipMemsetAsync(t_nullable, 0, 4, v.stream));
+      hipLaunchKernelGGL(k_snap_transpose, dim3(rgrid), dim3(256), 0,
+                         v.stream, x, t_perm, n, t_nullable);
+      HIP_TRY(hipEventRecord(ev_b1, v.stream));
+      HIP_TRY(hipMemcpyAsync(&sn->nullable_cols, t_nullable, 4,
+                             hipMemcpyDeviceToHost, v.stream));
+      HIP_TRY(hipStreamSynchronize(v.stream));
+
+      const uint64_t n_part = snap_grid(n) * (kSnapThreads / 64);
+      HIP_TRY(hipMalloc(&sn->d_partials,
+                        n_part * kSnapPartialStride * sizeof(uint64_t)));
+      sn->device_bytes += n_part * kSnapPartialStride * sizeof(uint64_t);
+    } else {
+      HIP_TRY(hipEventRecord(ev_b1, v.stream));
+      HIP_TRY(hipStreamSynchronize(v.stream));
+    }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev_b0, ev_b1));
+    sn->build_ms = ms;
+    // tmp's destructor frees the AoS temporaries here
+  }
+  guard.sn = nullptr;
+  *out = sn;
+  return 0;
+}
+
+extern "C" {
+
+int yb_gpu_snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out) {
+  return ybgint::snapshot_build(s, out, false);
+}
+
+int yb_gpu_snapshot_info(ybg_snapshot_t* sn, ybg_snapshot_info_t* out) {
+  memset(out, 0, sizeof(*out));
+  out->n_rows = sn->n_rows;
+  out->entries_seen = sn->entries_seen;
+  out->device_bytes = sn->device_bytes;
+  out->build_ms = sn->build_ms;
+  out->staged_value_cols = sn->staged_value_cols;
+  out->nullable_cols = sn->nullable_cols;
+  memcpy(out->restart_ht, sn->restart_ht, sn->restart_len);
+  out->restart_ht_len = sn->restart_len;
+  return 0;
+}
+
+int yb_gpu_snapshot_query(ybg_snapshot_t* sn, const ybg_snapshot_query_t* q,
+                          ybg_scan_result_t* out) {
+  int rc = snap_launch(sn, q->num_preds, q->preds, q->num_aggs, q->aggs);
+  if (rc) return rc;
+  return snap_finish(sn, q->num_aggs, q->aggs, out);
+}
+
+int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t* sn, double* query_ms) {
+  *query_ms = sn->last_query_ms;
+  return 0;
+}
+
+int yb_gpu_snapshot_close(ybg_snapshot_t* sn) {
+  if (sn->stream) HIP_WARN(hipStreamSynchronize(sn->stream));
+  snap_free(sn);
+  return 0;
+}
+
+}  // extern "C"

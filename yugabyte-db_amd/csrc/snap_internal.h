@@ -1,0 +1,73 @@
+// yugabyte-db_amd/csrc/snap_internal.h — library-internal seam between the
+// block scan (scan_gpu.hip) and the columnar snapshot (snap_gpu.hip). Not
+// part of the C ABI.
+#ifndef YBG_SNAP_INTERNAL_H
+#define YBG_SNAP_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "scan_device.h"
+
+namespace ybgint {
+
+int set_err(int code, const std::string& msg);
+
+// What the snapshot build needs to know about a fed scan handle.
+struct ScanView {
+  const ybg_scan_spec_t* spec;
+  hipStream_t stream;
+  uint64_t n_ivs;
+  bool fed;             // feed_blocks uploaded a block set
+  bool bloom_rejected;  // feed proved the scan empty: nothing uploaded
+  bool pruned_by_options;  // feed dropped blocks by a leading-key IN /
+                           // IN_RANGE predicate of the spec
+};
+ScanView scan_view(ybg_scan_t* s);
+
+// Scan statistics of a flags pre-pass (what yb_gpu_scan_aggregate reports
+// next to the aggregates).
+struct ScanStats {
+  uint64_t entries, scanned, errs;
+  uint8_t restart_ht[YBG_MAX_HT];
+  uint32_t restart_len;
+};
+
+// The device part of row materialization, shared by yb_gpu_scan_next_batch
+// and the snapshot build. Both run under `d` (uploaded to the kernels'
+// constant spec) with `d_aux` as its aux buffer.
+//   scan_flags_pass: k_scan<2,3> in write_all_flags form — resolves head-row
+//     ownership for every interval into the handle's flags array. Async.
+//   scan_flags_stats: folds that pass's wave partials + head records
+//     (entries, visible rows, errors, restart data). Synchronizes.
+//   scan_emit_pass: k_emit into `ec` (ec.head_consumed is set here).
+//     d_counters: 4 x u64 {rows, varlen, overflow, err}, zeroed here;
+//     copied to ctr after the kernel. Synchronizes.
+int scan_flags_pass(ybg_scan_t* s, const ybgdev::DevSpec& d,
+                    const uint8_t* d_aux);
+int scan_flags_stats(ybg_scan_t* s, const ybgdev::DevSpec& d,
+                     ScanStats* out);
+int scan_emit_pass(ybg_scan_t* s, const uint8_t* d_aux, ybgdev::EmitCtx ec,
+                   unsigned long long* d_counters,
+                   unsigned long long ctr[4]);
+
+// yb_gpu_snapshot_build's body. allow_option_pruned: accept a handle whose
+// fed block set was pruned by its own option predicate — only sound when
+// every query will carry that predicate (the YBG_STAGE mode); the public
+// entry point refuses such handles.
+int snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
+                   bool allow_option_pruned);
+
+// YBG_STAGE=1 transparent mode (scan_gpu.hip calls into snap_gpu.hip).
+// can the spec's predicates/aggregates be answered from a snapshot?
+bool stage_eligible(const ybg_scan_spec_t& spec);
+// async launch of the handle spec's query on the snapshot's stream
+int stage_launch(ybg_snapshot_t* snap, const ybg_scan_spec_t& spec);
+// wait + fetch; query_ms: the query kernel + reduce time
+int stage_finish(ybg_snapshot_t* snap, const ybg_scan_spec_t& spec,
+                 ybg_scan_result_t* out, double* query_ms);
+
+}  // namespace ybgint
+
+#endif  // YBG_SNAP_INTERNAL_H
