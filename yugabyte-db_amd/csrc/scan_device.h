@@ -13,11 +13,6 @@
 #endif
 #define DEV YBG_DEV_QUAL
 
-// tail-update strategy for the fast scanner (see scan_batch_fast)
-#ifndef YBG_TAILMODE
-#define YBG_TAILMODE 0
-#endif
-
 #ifdef YBG_HOST_SIM
 // host shims for the HIP bit-cast intrinsics
 static inline double __longlong_as_double(long long v) {
@@ -545,8 +540,10 @@ struct Rdr {
       k -= 8;
     }
   }
-  // 8 bytes at position + off (k + off + 7 must be < 32, i.e. call
-  // align8() first when off can reach 16)
+  // 8 bytes at position + off. Valid for k + off <= 23 only: from 24 on
+  // the mask selection below still returns window bytes 16..23. Every
+  // caller is inside that range: peek8_at(8) anywhere (k < 16), and
+  // peek8_at(16) only after align8() (k < 8).
   DEV uint64_t peek8_at(uint32_t off) const {
     uint32_t kk = k + off;
     uint64_t m1 = (uint64_t)0 - (uint64_t)(kk >= 8);
@@ -570,7 +567,7 @@ struct Rdr {
       const uint64_t* q = (const uint64_t*)base;
       q2 = q[2];
       q3 = q[3];
-#if !defined(YBG_NO_PF) && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
       // sliding L2 prefetch: one extra independent load per 64 consumed
       // bytes, ~192 B ahead of the stream (device buffers carry 256 B of
       // tail slack for this). The asm keeps the otherwise-dead load.
@@ -2279,6 +2276,15 @@ DEV long long group_export_value(int op, long long raw,
   return raw;
 }
 
+// Initial group-table value per aggregate op (k_group_init and the host
+// simulator's table setup).
+DEV long long group_init_value(int op) {
+  if (op == YBG_AGG_MIN_INT64) return 0x7fffffffffffffffll;
+  if (op == YBG_AGG_MAX_INT64) return (long long)0x8000000000000000ll;
+  if (op == YBG_AGG_MIN_DOUBLE) return (long long)~0ull;  // ordered-u64 max
+  return 0;  // MAX_DOUBLE: ordered-u64 min; SUM/COUNT: zero
+}
+
 // Deferred head-row record for the single-pass GROUP kernel: the head
 // row's raw operands (ownership unknown until the lane relay / cont-flag
 // resolution). agg_datum is fixed-size for a stable memory layout; the
@@ -2292,12 +2298,13 @@ struct GroupHead {
   uint32_t hit;
 };
 
-template <int NA>
-DEV void group_accum(const DevSpec& sp, const GroupCtx& gc,
-                     const RowCtxT<NA>& rc) {
-#if YBG_GABL == 1
-  return;
-#endif
+// Accumulate one matching row into its group's table slot. SRC is the live
+// row context (RowCtxT) or a deferred head record (GroupHead: the
+// heads-resolution pass and the in-kernel not-consumed head path); both
+// carry the same grp_* / agg_* field names.
+template <int NA, class SRC>
+DEV void group_accum_from(const DevSpec& sp, const GroupCtx& gc,
+                          const SRC& rc) {
   uint64_t slot;
   if (rc.grp_null) {
     slot = gc.cap;  // the NULL-key group
@@ -2314,9 +2321,6 @@ DEV void group_accum(const DevSpec& sp, const GroupCtx& gc,
       return;
     }
   }
-#if YBG_GABL == 2
-  return;
-#endif
   long long* v = gc.vals + slot * YBG_MAX_AGGS;
   unsigned long long* c = gc.cnts + slot * YBG_MAX_AGGS;
 #pragma unroll
@@ -2360,69 +2364,16 @@ DEV void group_accum(const DevSpec& sp, const GroupCtx& gc,
   }
 }
 
-// Same accumulate from a deferred head record (the heads-resolution pass
-// and the in-kernel not-consumed head path).
+template <int NA>
+DEV void group_accum(const DevSpec& sp, const GroupCtx& gc,
+                     const RowCtxT<NA>& rc) {
+  group_accum_from<NA>(sp, gc, rc);
+}
+
 template <int NA>
 DEV void group_accum_rec(const DevSpec& sp, const GroupCtx& gc,
                          const GroupHead& r) {
-  uint64_t slot;
-  if (r.grp_null) {
-    slot = gc.cap;
-    if (ybg_atomic_load_u32(&gc.state[slot]) != 1)
-      ybg_atomic_store_rel_u32(&gc.state[slot], 1u);
-  } else {
-    bool is_str = r.grp_len != 0;
-    uint64_t kv = is_str ? (((uint64_t)r.grp_len << 40) |
-                            (r.grp_datum - (uint64_t)(uintptr_t)gc.data))
-                         : r.grp_datum;
-    slot = grp_find_or_insert(gc, kv, is_str);
-    if (slot == ~0ull) {
-      atomicAdd(gc.overflow, 1ull);
-      return;
-    }
-  }
-#if YBG_GABL == 2
-  return;
-#endif
-  long long* v = gc.vals + slot * YBG_MAX_AGGS;
-  unsigned long long* c = gc.cnts + slot * YBG_MAX_AGGS;
-#pragma unroll
-  for (int g = 0; g < NA; ++g) {
-    if (g >= sp.num_aggs) continue;
-    int op = sp.aggs[g].op;
-    bool isnull =
-        (op == YBG_AGG_COUNT_STAR) ? false : ((r.agg_null >> g) & 1);
-    if (isnull) continue;
-    uint64_t d = r.agg_datum[g];
-    switch (op) {
-      case YBG_AGG_COUNT_STAR:
-      case YBG_AGG_COUNT:
-        atomicAdd((unsigned long long*)&v[g], 1ull);
-        break;
-      case YBG_AGG_SUM_INT64:
-        atomicAdd((unsigned long long*)&v[g], d);
-        break;
-      case YBG_AGG_SUM_DOUBLE:
-        group_sum_f64_fixed(gc, slot, g, d);
-        break;
-      case YBG_AGG_MIN_INT64:
-        ybg_atomic_min_i64(&v[g], (long long)d);
-        break;
-      case YBG_AGG_MAX_INT64:
-        ybg_atomic_max_i64(&v[g], (long long)d);
-        break;
-      case YBG_AGG_MIN_DOUBLE:
-        ybg_atomic_min_u64((unsigned long long*)&v[g], f64_ordered(d));
-        break;
-      case YBG_AGG_MAX_DOUBLE:
-        ybg_atomic_max_u64((unsigned long long*)&v[g], f64_ordered(d));
-        break;
-      default:
-        break;
-    }
-    if (op != YBG_AGG_COUNT_STAR && op != YBG_AGG_COUNT)
-      atomicAdd(&c[g], 1ull);
-  }
+  group_accum_from<NA>(sp, gc, r);
 }
 
 // Write one materialized row (PgTableRow analog — dockv/pg_row.h:91-179).
@@ -2502,47 +2453,6 @@ DEV void emit_row(const DevSpec& sp, EmitCtx* ec, const RowCtxT<NA>& rc,
 // the accumulators; the caller re-runs the batch through the general path.
 // Semantics are pinned against scan_one_interval by sim + GPU parity tests.
 // ---------------------------------------------------------------------------
-
-DEV void u128_shr(uint64_t* hi, uint64_t* lo, uint32_t s) {
-  if (s >= 64) {
-    *lo = s >= 128 ? 0 : (*hi >> (s - 64));
-    *hi = 0;
-  } else if (s) {
-    *lo = (*lo >> s) | (*hi << (64 - s));
-    *hi >>= s;
-  }
-}
-
-DEV void u128_shl(uint64_t* hi, uint64_t* lo, uint32_t s) {
-  if (s >= 64) {
-    *hi = s >= 128 ? 0 : (*lo << (s - 64));
-    *lo = 0;
-  } else if (s) {
-    *hi = (*hi << s) | (*lo >> (64 - s));
-    *lo <<= s;
-  }
-}
-
-// Splice n (1..16) big-endian bytes (sv_hi:sv_lo, first byte at sv_hi's
-// MSB) into the 16-byte register tail at SIGNED tail byte offset o
-// (o = key_pos - (ukey_len - 16)); bytes falling outside [0,16) drop out.
-// Replaces a per-byte tail_patch loop (~18 instructions per byte) with
-// ~30 instructions per RANGE.
-DEV void tail_splice(uint64_t* thi, uint64_t* tlo, int32_t o, uint32_t n,
-                     uint64_t sv_hi, uint64_t sv_lo) {
-  if (o <= -(int32_t)n || o >= 16) return;
-  uint64_t mh = n >= 8 ? ~0ull : (~0ull << (64 - 8 * n));
-  uint64_t ml = n <= 8 ? 0ull : (n >= 16 ? ~0ull : (~0ull << (128 - 8 * n)));
-  if (o >= 0) {
-    u128_shr(&sv_hi, &sv_lo, 8 * (uint32_t)o);
-    u128_shr(&mh, &ml, 8 * (uint32_t)o);
-  } else {
-    u128_shl(&sv_hi, &sv_lo, 8 * (uint32_t)(-o));
-    u128_shl(&mh, &ml, 8 * (uint32_t)(-o));
-  }
-  *thi = (*thi & ~mh) | (sv_hi & mh);
-  *tlo = (*tlo & ~ml) | (sv_lo & ml);
-}
 
 // Accumulate ONE row's aggregate operand (acc_row's per-slot body).
 DEV void combine_datum(int op, uint64_t* val, uint64_t* cnt, uint64_t v) {
@@ -2624,21 +2534,6 @@ inline bool fast_eligible(const DevSpec& d) {
 
 #ifndef YBG_FABORT
 #define YBG_FABORT(n) return 0
-#endif
-
-// YBG_ABL: perf-forensics ablations of scan_batch_fast (results WRONG by
-// design — never in a default build): 1 = skip register-tail patches and
-// force visibility true; 2 = skip packed-value decode; 3 = skip the
-// per-row finalize accumulation.
-#ifndef YBG_ABL
-#define YBG_ABL 0
-#endif
-
-// YBG_GABL: grouped-kernel ablations (results WRONG by design, never in
-// a default build): 1 = skip the group hash table entirely (measures the
-// scan/eval side alone); 2 = probe/insert but skip the per-agg atomics.
-#ifndef YBG_GABL
-#define YBG_GABL 0
 #endif
 
 // Returns 1 = batch done (accumulators updated), 0 = abort (accumulators
@@ -2854,11 +2749,8 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       {
         // changed bytes: LDS only below rkb (the restart row-compare
         // source), register tail inside the window, nothing in between.
-        // YBG_TAILMODE selects the tail-update strategy (A/B-measured):
-        //   0 per-byte tail_patch from window bytes (needs align8 + w3)
-        //   1 range splice sourced by direct loads from the entry bytes
-        //   2 range splice sourced by window peeks
-#if YBG_TAILMODE == 0
+        // The tail is patched per byte from window bytes (needs align8 +
+        // w3); range splices from loads or window peeks measured slower.
         rdr.align8();
         w = rdr.peek8();
         w2 = rdr.peek8_at(8);
@@ -2885,16 +2777,12 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
           for (uint32_t i = 0; i < ns1; ++i) {
             uint8_t b = body_byte(hl + i);
             key[sp + i] = b;
-#if YBG_ABL != 1
             tail_patch(&thi, &tlo, ukey, sp + i, b);
-#endif
           }
           for (uint32_t i = 0; i < ns2; ++i) {
             uint8_t b = body_byte(hl + ns1 + i);
             key[ns2s + i] = b;
-#if YBG_ABL != 1
             tail_patch(&thi, &tlo, ukey, ns2s + i, b);
-#endif
           }
         } else {
           // single-version shape: separate loops, LDS bounded below rkb
@@ -2902,42 +2790,11 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
             key[sp + i] = body_byte(hl + i);
           for (uint32_t i = 0; i < lds2; ++i)
             key[ns2s + i] = body_byte(hl + ns1 + i);
-#if YBG_ABL != 1
           for (uint32_t i = 0; i < ns1; ++i)
             tail_patch(&thi, &tlo, ukey, sp + i, body_byte(hl + i));
           for (uint32_t i = 0; i < ns2; ++i)
             tail_patch(&thi, &tlo, ukey, ns2s + i, body_byte(hl + ns1 + i));
-#endif
         }
-#else
-        uint32_t lds_n = sp < rkb ? (rkb - sp < ns1 ? rkb - sp : ns1) : 0;
-        for (uint32_t i = 0; i < lds_n; ++i)
-          key[sp + i] = p[hl + i];
-        uint32_t lds2 = ns2s < rkb ? (rkb - ns2s < ns2 ? rkb - ns2s : ns2)
-                                   : 0;
-        for (uint32_t i = 0; i < lds2; ++i)
-          key[ns2s + i] = p[hl + ns1 + i];
-        const int32_t T = (int32_t)ukey - 16;
-#if YBG_TAILMODE == 2
-        rdr.align8();
-        uint64_t s1h = __builtin_bswap64(rdr.peek8_at(hl));
-        uint64_t s1l =
-            ns1 > 8 ? __builtin_bswap64(rdr.peek8_at(hl + 8)) : 0;
-        uint64_t s2h =
-            ns2 ? __builtin_bswap64(hl + ns1 <= 17
-                                        ? rdr.peek8_at(hl + ns1)
-                                        : load_u64_una(p + hl + ns1))
-                : 0;
-#else
-        uint64_t s1h = __builtin_bswap64(load_u64_una(p + hl));
-        uint64_t s1l =
-            ns1 > 8 ? __builtin_bswap64(load_u64_una(p + hl + 8)) : 0;
-        uint64_t s2h =
-            ns2 ? __builtin_bswap64(load_u64_una(p + hl + ns1)) : 0;
-#endif
-        tail_splice(&thi, &tlo, (int32_t)sp - T, ns1, s1h, s1l);
-        if (ns2) tail_splice(&thi, &tlo, (int32_t)ns2s - T, ns2, s2h, 0);
-#endif
       }
       (void)inc;
       rdr.consume(nb);
@@ -2973,11 +2830,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
     // row boundary
     if (kchg) {
       if (row_open) {
-#if YBG_ABL == 3
-        if (false) {
-#else
         if (found) {
-#endif
           bool hit = (pred_pass & sp.value_pred_mask) == sp.value_pred_mask;
           if (in_head) {
             ho->scanned += 1;
@@ -3026,13 +2879,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
     const uint32_t vb0 =
         er.value_len ? (uint32_t)(rdr.peek8() & 0xff) : 0u;
     if (YBG_UNLIKELY(vb0 == kHybridTimeByte)) YBG_FABORT(23);
-#if YBG_ABL == 1
-    const bool visible = true;
-#else
     const bool visible =
         u128_slice_cmp(ht_hi, ht_lo, ht_sz, sp.reg_lim.hi, sp.reg_lim.lo,
                        sp.reg_lim.len) >= 0;
-#endif
     if (visible) {
       if (YBG_UNLIKELY(sp.track_restart)) {
         if (u128_slice_cmp(ht_hi, ht_lo, ht_sz, sp.read.hi, sp.read.lo,
@@ -3048,16 +2897,6 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       }
       if (!base_seen) {
         base_seen = true;
-#if YBG_ABL == 2
-        if (true) {
-          found = true;
-          pred_pass = sp.value_pred_mask;
-          agg_null = 0;
-          rdr.seek(q);
-          p = q;
-          continue;
-        } else
-#endif
         if (YBG_LIKELY(er.value_len == sp.v2_fixed_len && vb0 == kPackedV2B &&
                        (rdr.peek8() & 0xff8000u) == 0)) {
           const uint8_t* value = rdr.pos();
@@ -3174,32 +3013,80 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
   return 1;
 }
 
+// Finalize one assembled row of batch j (doc_rowwise_iterator row
+// boundary): bounds, predicates, then the head-record or main accumulate,
+// row emission and the group accumulate / head deferral. rkp = the row's
+// key bytes.
+template <int NA, bool EMIT, bool GROUP>
+DEV void finalize_row(const DevSpec& sp, const RowCtxT<NA>& rc,
+                      const uint8_t* rkp, uint32_t rk_len,
+                      const uint8_t* aux, bool in_head, uint64_t j,
+                      uint32_t* scanned, uint32_t* matched,
+                      uint64_t* agg_val, uint64_t* agg_cnt, HeadOut<NA>* ho,
+                      EmitCtx* ec, uint64_t row_sort_key, const GroupCtx* gc,
+                      GroupHead* gh_out) {
+  if (!rc.found || !in_bounds(sp, rkp, rk_len, aux)) return;
+  // explicit in_head/main branches (never a runtime-selected pointer):
+  // both destinations must stay register-promotable
+  bool hit = (rc.pred_pass & sp.value_pred_mask) == sp.value_pred_mask &&
+             eval_key_preds(sp, rkp, rk_len, aux);
+  if (in_head) {
+    ho->scanned += 1;
+    if (hit) {
+      ho->matched += 1;
+      acc_row(sp, rc, ho->val, ho->cnt);
+    }
+  } else {
+    *scanned += 1;
+    if (hit) {
+      *matched += 1;
+      acc_row(sp, rc, agg_val, agg_cnt);
+    }
+  }
+  if (!hit) return;
+  if (EMIT && (!in_head || ec->head_consumed[j] == 0))
+    emit_row(sp, ec, rc, rkp, rk_len, row_sort_key);
+  if (GROUP) {
+    if (!in_head) {
+      group_accum(sp, *gc, rc);
+    } else {
+      // defer the head row (ownership unknown): raw operands
+      gh_out->grp_datum = rc.grp_datum;
+      gh_out->grp_len = rc.grp_len;
+      gh_out->grp_null = rc.grp_null ? 1u : 0u;
+      gh_out->agg_null = rc.agg_null;
+#pragma unroll
+      for (int g = 0; g < NA; ++g) gh_out->agg_datum[g] = rc.agg_datum[g];
+      gh_out->hit = 1;
+    }
+  }
+}
+
 // Scan the interval range [j, j_hi) as ONE continuous stream (j_hi = j+1
 // is the classic one-interval form). The batch DEFERS its first (head)
 // row and WALKS its last row into interval j_hi; interior interval
 // boundaries are just stream positions (contiguous intervals of one block
-// continue without re-initializing the reader). iv_flags, when non-null
+// continue without re-initializing the reader). EMIT needs ec and the two
+// emit buffers, GROUP needs gc and gh_out. iv_flags, when non-null
 // (the emit flags pre-pass), receives per-INTERVAL head-consumption:
 // iv_flags[i] = 1 iff interval i's first row is a continuation of a row
 // from interval i-1 — exactly what k_emit's per-interval workers need.
 template <int NA, bool EMIT = false, bool GROUP = false>
 DEV bool scan_one_interval(const DevSpec& sp, const uint8_t* data,
                            const uint64_t* block_offsets, const Interval* ivs,
-                           uint64_t n_ivs, uint64_t j, const uint8_t* aux,
-                           uint8_t* key, uint8_t* rk_save, uint64_t* bht,
+                           uint64_t n_ivs, uint64_t j, uint64_t j_hi,
+                           const uint8_t* aux, uint8_t* key,
+                           uint8_t* rk_save, uint64_t* bht,
                            uint32_t* entries,
                            uint32_t* scanned, uint32_t* matched,
                            uint64_t* agg_val, uint64_t* agg_cnt,
                            HeadOut<NA>* ho, bool* walked_next_out,
+                           uint32_t* iv_flags,
                            EmitCtx* ec = nullptr,
                            uint64_t* emit_datums = nullptr,
                            uint32_t* emit_lens = nullptr,
                            const GroupCtx* gc = nullptr,
-                           const uint32_t* head_flags = nullptr,
-                           GroupHead* gh_out = nullptr,
-                           uint64_t j_hi_in = 0,
-                           uint32_t* iv_flags = nullptr) {
-  const uint64_t j_hi = j_hi_in ? j_hi_in : j + 1;
+                           GroupHead* gh_out = nullptr) {
   Interval iv = ivs[j];
   const uint8_t* blk = data + block_offsets[iv.block];
   const uint8_t* p = blk + iv.start;
@@ -3322,49 +3209,10 @@ DEV bool scan_one_interval(const DevSpec& sp, const uint8_t* data,
     }
     if (row_change) {
       if (row_open) {
-        // finalize previous row (doc_rowwise_iterator row boundary)
-        const uint8_t* rkp = (rkb && !EMIT) ? key : rk_save;
-        if (rc.found && in_bounds(sp, rkp, rk_len, aux)) {
-          // explicit in_head/main branches (never a runtime-selected
-          // pointer): both destinations must stay register-promotable
-          bool hit = (rc.pred_pass & sp.value_pred_mask) ==
-                         sp.value_pred_mask &&
-                     eval_key_preds(sp, rkp, rk_len, aux);
-          if (in_head) {
-            ho->scanned += 1;
-            if (hit) {
-              ho->matched += 1;
-              acc_row(sp, rc, ho->val, ho->cnt);
-            }
-          } else {
-            *scanned += 1;
-            if (hit) {
-              *matched += 1;
-              acc_row(sp, rc, agg_val, agg_cnt);
-            }
-          }
-          if (hit) {
-            if (EMIT && (!in_head || ec->head_consumed[j] == 0))
-              emit_row(sp, ec, rc, rkp, rk_len, row_sort_key);
-            if (GROUP) {
-              if (!in_head) {
-                group_accum(sp, *gc, rc);
-              } else if (gh_out) {
-                // defer the head row (ownership unknown): raw operands
-                gh_out->grp_datum = rc.grp_datum;
-                gh_out->grp_len = rc.grp_len;
-                gh_out->grp_null = rc.grp_null ? 1u : 0u;
-                gh_out->agg_null = rc.agg_null;
-#pragma unroll
-                for (int g = 0; g < NA; ++g)
-                  gh_out->agg_datum[g] = rc.agg_datum[g];
-                gh_out->hit = 1;
-              } else if (head_flags && head_flags[j] == 0) {
-                group_accum(sp, *gc, rc);
-              }
-            }
-          }
-        }
+        finalize_row<NA, EMIT, GROUP>(
+            sp, rc, (rkb && !EMIT) ? key : rk_save, rk_len, aux, in_head, j,
+            scanned, matched, agg_val, agg_cnt, ho, ec, row_sort_key, gc,
+            gh_out);
         in_head = false;
         row_open = false;
         if (cur_iv >= j_hi) break;  // tail walk ended at a new row
@@ -3390,44 +3238,10 @@ DEV bool scan_one_interval(const DevSpec& sp, const uint8_t* data,
     rdr.seek(q);
     p = q;
   }
-  const uint8_t* rkp_end = (rkb && !EMIT) ? key : rk_save;
-  if (!fail && row_open && rc.found && in_bounds(sp, rkp_end, rk_len, aux)) {
-    bool hit = (rc.pred_pass & sp.value_pred_mask) == sp.value_pred_mask &&
-               eval_key_preds(sp, rkp_end, rk_len, aux);
-    if (in_head) {
-      ho->scanned += 1;
-      if (hit) {
-        ho->matched += 1;
-        acc_row(sp, rc, ho->val, ho->cnt);
-      }
-    } else {
-      *scanned += 1;
-      if (hit) {
-        *matched += 1;
-        acc_row(sp, rc, agg_val, agg_cnt);
-      }
-    }
-    if (hit) {
-      if (EMIT && (!in_head || ec->head_consumed[j] == 0))
-        emit_row(sp, ec, rc, rkp_end, rk_len, row_sort_key);
-      if (GROUP) {
-        if (!in_head) {
-          group_accum(sp, *gc, rc);
-        } else if (gh_out) {
-          gh_out->grp_datum = rc.grp_datum;
-          gh_out->grp_len = rc.grp_len;
-          gh_out->grp_null = rc.grp_null ? 1u : 0u;
-          gh_out->agg_null = rc.agg_null;
-#pragma unroll
-          for (int g = 0; g < NA; ++g)
-            gh_out->agg_datum[g] = rc.agg_datum[g];
-          gh_out->hit = 1;
-        } else if (head_flags && head_flags[j] == 0) {
-          group_accum(sp, *gc, rc);
-        }
-      }
-    }
-  }
+  if (!fail && row_open)  // the stream ended inside a row
+    finalize_row<NA, EMIT, GROUP>(
+        sp, rc, (rkb && !EMIT) ? key : rk_save, rk_len, aux, in_head, j,
+        scanned, matched, agg_val, agg_cnt, ho, ec, row_sort_key, gc, gh_out);
   *walked_next_out = walked_next;
   return !fail;
 }
@@ -3435,6 +3249,20 @@ DEV bool scan_one_interval(const DevSpec& sp, const uint8_t* data,
 // ---------------------------------------------------------------------------
 // Host-side spec translation (shared by the ABI and the host simulator).
 // ---------------------------------------------------------------------------
+
+// Unpack a restart-min record {hi, lo, len} (big-endian encoded-HT bytes,
+// first byte at hi's MSB — htlim's packing below) into out[YBG_MAX_HT];
+// returns the byte count (0 = no restart needed).
+inline uint32_t unpack_restart_ht(uint64_t hi, uint64_t lo, uint64_t len,
+                                  uint8_t* out) {
+  uint32_t n = (uint32_t)len;
+  if (n > YBG_MAX_HT) n = YBG_MAX_HT;
+  for (uint32_t i = 0; i < n; ++i)
+    out[i] = (uint8_t)(
+        (i < 8 ? hi >> (56 - 8 * i) : lo >> (56 - 8 * (i - 8))) & 0xff);
+  return n;
+}
+
 inline void build_dev_spec(const ybg_scan_spec_t* spec, DevSpec* dp,
                            unsigned char* aux, uint32_t* aux_len,
                            uint32_t aux_cap) {

@@ -59,6 +59,87 @@ namespace {
 __constant__ DevSpec c_spec;
 
 // ---------------------------------------------------------------------------
+// Scaffolding shared by the scan kernels
+// ---------------------------------------------------------------------------
+
+// batch j = ivb CONSECUTIVE intervals — or one BLOCK's intervals when
+// batch_lo is set (block-aligned batches keep lanes phase-locked on the
+// 16-entry restart cadence)
+__device__ __forceinline__ void batch_bounds(
+    const uint64_t* __restrict__ batch_lo, uint64_t j, uint64_t ivb,
+    uint64_t n_ivs, uint64_t* lo, uint64_t* hi) {
+  *lo = batch_lo ? batch_lo[j] : j * ivb;
+  *hi = batch_lo ? batch_lo[j + 1] : *lo + ivb;
+  if (*hi > n_ivs) *hi = n_ivs;
+}
+
+// Wave restart-minimum into the wave's partial record, run by lane 0:
+// lane l's candidate {hi, lo, len} sits at slots[(tid + l) * stride + off]
+// (cold: len == 0 for every lane unless track_restart saw candidates).
+__device__ __forceinline__ void wave_restart_min(
+    const uint64_t* slots, int stride, int off, uint64_t* __restrict__ prec) {
+  uint64_t mh = 0, ml = 0, mn = 0;
+  for (int l = 0; l < 64; ++l) {
+    const uint64_t* rr = slots + (size_t)(threadIdx.x + l) * stride + off;
+    if (rr[2] == 0) continue;
+    if (mn == 0 || u128_slice_cmp(rr[0], rr[1], (uint32_t)rr[2], mh, ml,
+                                  (uint32_t)mn) < 0) {
+      mh = rr[0];
+      ml = rr[1];
+      mn = rr[2];
+    }
+  }
+  prec[4 + 2 * YBG_MAX_AGGS] = mh;
+  prec[4 + 2 * YBG_MAX_AGGS + 1] = ml;
+  prec[4 + 2 * YBG_MAX_AGGS + 2] = mn;
+}
+
+// Kernel epilogue: fold the wave's counters and aggregates into its partial
+// record (fixed lane order => deterministic), then the restart minimum.
+// Called by every thread of the block; red_val / red_cnt are kThreads-sized
+// LDS arrays.
+template <int NA>
+__device__ __forceinline__ void wave_fold_partials(
+    const DevSpec& sp, uint32_t entries, uint32_t scanned, uint32_t matched,
+    uint32_t errs, const uint64_t* agg_val, const uint64_t* agg_cnt,
+    uint64_t* red_val, uint64_t* red_cnt, const uint64_t* rslots,
+    int rstride, int roff, uint64_t* __restrict__ partials) {
+  unsigned lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    entries += __shfl_down(entries, off);
+    scanned += __shfl_down(scanned, off);
+    matched += __shfl_down(matched, off);
+    errs += __shfl_down(errs, off);
+  }
+  uint64_t wave_id = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
+  uint64_t* prec = partials + wave_id * kPartialStride;
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    if (g >= sp.num_aggs) continue;
+    red_val[threadIdx.x] = agg_val[g];
+    red_cnt[threadIdx.x] = agg_cnt[g];
+    __syncthreads();
+    if (lane == 0) {
+      uint64_t av = 0, ac = 0;
+      for (int l = 0; l < 64; ++l)
+        combine1(sp.agg_op[g], &av, &ac, red_val[threadIdx.x + l],
+                 red_cnt[threadIdx.x + l]);
+      prec[4 + 2 * g] = av;
+      prec[4 + 2 * g + 1] = ac;
+    }
+    __syncthreads();
+  }
+  if (lane == 0) {
+    prec[0] = entries;
+    prec[1] = scanned;
+    prec[2] = matched;
+    prec[3] = errs;
+    wave_restart_min(rslots, rstride, roff, prec);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Phase-1 scan kernel (aggregate mode): one thread per interval
 // ---------------------------------------------------------------------------
 
@@ -90,9 +171,6 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
   const uint32_t gtid = blockIdx.x * kThreads + threadIdx.x;
   uint8_t* rk_save = rk_save_buf + (size_t)gtid * kKeyCap;
   const uint64_t span = (uint64_t)gridDim.x * kThreads;
-  // batch = ivb CONSECUTIVE intervals — or one BLOCK's intervals when
-  // batch_lo is set (block-aligned batches keep lanes phase-locked on
-  // the 16-entry restart cadence)
   const uint64_t n_work = retry_ids ? *retry_n : n_bat;
   constexpr int kHS = 2 * NA + 2;  // bheads stride
 
@@ -109,17 +187,19 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
     const uint64_t j = retry_ids ? retry_ids[i0] : i0;
     HeadOut<NA> ho;
     bool walked_next = false;
-    const uint64_t lo = batch_lo ? batch_lo[j] : j * ivb;
-    uint64_t hi = batch_lo ? batch_lo[j + 1] : lo + ivb;
-    if (hi > n_ivs) hi = n_ivs;
-    if (!scan_one_interval<NA>(sp, data, block_offsets, ivs, n_ivs, lo,
+    uint64_t lo, hi;
+    batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
+    if (!scan_one_interval<NA>(sp, data, block_offsets, ivs, n_ivs, lo, hi,
                                aux, key, rk_save, bht, &entries, &scanned,
                                &matched, agg_val, agg_cnt, &ho,
-                               &walked_next, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, hi,
+                               &walked_next,
                                write_all_flags ? iv_flags : nullptr)) {
       errs += 1;
     }
+    // head record + walked flag, written out here and in k_scan_fast: moved
+    // into a shared inline function (any signature) these nine lines changed
+    // both kernels' register allocation, and k_scan_fast<3,4,false> went
+    // from 3 to 4 waves/SIMD
     uint64_t* hr = bheads + j * kHS;
 #pragma unroll
     for (int g = 0; g < NA; ++g) {
@@ -131,57 +211,10 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
     walked[j] = walked_next ? 1 : 0;
   }
 
-  // wave reduction into partials (fixed lane order => deterministic)
-  {
-    unsigned lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      entries += __shfl_down(entries, off);
-      scanned += __shfl_down(scanned, off);
-      matched += __shfl_down(matched, off);
-      errs += __shfl_down(errs, off);
-    }
-    __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
-    uint64_t wave_id = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
-#pragma unroll
-    for (int g = 0; g < NA; ++g) {
-      if (g >= sp.num_aggs) continue;
-      red_val[threadIdx.x] = agg_val[g];
-      red_cnt[threadIdx.x] = agg_cnt[g];
-      __syncthreads();
-      if (lane == 0) {
-        uint64_t av = 0, ac = 0;
-        for (int l = 0; l < 64; ++l)
-          combine1(sp.agg_op[g], &av, &ac, red_val[threadIdx.x + l],
-                   red_cnt[threadIdx.x + l]);
-        partials[wave_id * kPartialStride + 4 + 2 * g] = av;
-        partials[wave_id * kPartialStride + 4 + 2 * g + 1] = ac;
-      }
-      __syncthreads();
-    }
-    if (lane == 0) {
-      partials[wave_id * kPartialStride + 0] = entries;
-      partials[wave_id * kPartialStride + 1] = scanned;
-      partials[wave_id * kPartialStride + 2] = matched;
-      partials[wave_id * kPartialStride + 3] = errs;
-      // restart-min across the wave (cold: len==0 for every lane unless
-      // track_restart saw candidates)
-      uint64_t mh = 0, ml = 0, mn = 0;
-      for (int l = 0; l < 64; ++l) {
-        const uint64_t* rr = bht_scratch + (size_t)(threadIdx.x + l) * 6 + 3;
-        if (rr[2] == 0) continue;
-        if (mn == 0 || u128_slice_cmp(rr[0], rr[1], (uint32_t)rr[2], mh, ml,
-                                      (uint32_t)mn) < 0) {
-          mh = rr[0];
-          ml = rr[1];
-          mn = rr[2];
-        }
-      }
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS] = mh;
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 1] = ml;
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 2] = mn;
-    }
-  }
+  __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
+  wave_fold_partials<NA>(sp, entries, scanned, matched, errs, agg_val,
+                         agg_cnt, red_val, red_cnt, bht_scratch, 6, 3,
+                         partials);
 }
 
 // ---------------------------------------------------------------------------
@@ -221,9 +254,8 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
   for (uint64_t j = gtid; j < n_bat; j += span) {
     HeadOut<NA> ho;
     bool walked_next = false;
-    const uint64_t lo = batch_lo ? batch_lo[j] : j * ivb;
-    uint64_t hi = batch_lo ? batch_lo[j + 1] : lo + ivb;
-    if (hi > n_ivs) hi = n_ivs;
+    uint64_t lo, hi;
+    batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
     if (!scan_batch_fast<NA, NC, FUSE>(sp, data, block_offsets, ivs, n_ivs,
                                        lo, hi,
                              key, rmin, &entries, &scanned, &matched,
@@ -243,55 +275,10 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
     walked[j] = walked_next ? 1 : 0;
   }
 
-  // wave reduction into partials (fixed lane order => deterministic)
-  {
-    unsigned lane = threadIdx.x & 63;
-    uint32_t errs = 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      entries += __shfl_down(entries, off);
-      scanned += __shfl_down(scanned, off);
-      matched += __shfl_down(matched, off);
-    }
-    __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
-    uint64_t wave_id = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
-#pragma unroll
-    for (int g = 0; g < NA; ++g) {
-      if (g >= sp.num_aggs) continue;
-      red_val[threadIdx.x] = agg_val[g];
-      red_cnt[threadIdx.x] = agg_cnt[g];
-      __syncthreads();
-      if (lane == 0) {
-        uint64_t av = 0, ac = 0;
-        for (int l = 0; l < 64; ++l)
-          combine1(sp.agg_op[g], &av, &ac, red_val[threadIdx.x + l],
-                   red_cnt[threadIdx.x + l]);
-        partials[wave_id * kPartialStride + 4 + 2 * g] = av;
-        partials[wave_id * kPartialStride + 4 + 2 * g + 1] = ac;
-      }
-      __syncthreads();
-    }
-    if (lane == 0) {
-      partials[wave_id * kPartialStride + 0] = entries;
-      partials[wave_id * kPartialStride + 1] = scanned;
-      partials[wave_id * kPartialStride + 2] = matched;
-      partials[wave_id * kPartialStride + 3] = errs;
-      uint64_t mh = 0, ml = 0, mn = 0;
-      for (int l = 0; l < 64; ++l) {
-        const uint64_t* rr = rmin_scratch + (size_t)(threadIdx.x + l) * 3;
-        if (rr[2] == 0) continue;
-        if (mn == 0 || u128_slice_cmp(rr[0], rr[1], (uint32_t)rr[2], mh, ml,
-                                      (uint32_t)mn) < 0) {
-          mh = rr[0];
-          ml = rr[1];
-          mn = rr[2];
-        }
-      }
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS] = mh;
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 1] = ml;
-      partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 2] = mn;
-    }
-  }
+  // errs = 0: the fast scanner aborts a batch instead of failing it
+  __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
+  wave_fold_partials<NA>(sp, entries, scanned, matched, 0, agg_val, agg_cnt,
+                         red_val, red_cnt, rmin_scratch, 3, 0, partials);
 }
 
 // ---------------------------------------------------------------------------
@@ -334,9 +321,9 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(
     HeadOut<2> ho;
     bool wn = false;
     if (!scan_one_interval<2, true>(sp, data, block_offsets, ivs, n_ivs, j,
-                                    aux, key, rk_save, bht, &entries,
+                                    j + 1, aux, key, rk_save, bht, &entries,
                                     &scanned, &matched, agg_val, agg_cnt,
-                                    &ho, &wn, &ec, rb, lb)) {
+                                    &ho, &wn, nullptr, &ec, rb, lb)) {
       atomicAdd(err_counter, 1ull);
     }
   }
@@ -355,15 +342,7 @@ __global__ void k_group_init(DevSpec sp, GroupCtx gc) {
     gc.state[i] = 0;
     gc.gkey[i] = 0;
     for (int g = 0; g < sp.num_aggs; ++g) {
-      long long init = 0;
-      if (sp.aggs[g].op == YBG_AGG_MIN_INT64) init = 0x7fffffffffffffffll;
-      else if (sp.aggs[g].op == YBG_AGG_MAX_INT64)
-        init = (long long)0x8000000000000000ll;
-      else if (sp.aggs[g].op == YBG_AGG_MIN_DOUBLE)
-        init = (long long)~0ull;  // ordered-u64 domain max
-      else if (sp.aggs[g].op == YBG_AGG_MAX_DOUBLE)
-        init = 0;                 // ordered-u64 domain min
-      gc.vals[i * YBG_MAX_AGGS + g] = init;
+      gc.vals[i * YBG_MAX_AGGS + g] = group_init_value(sp.aggs[g].op);
       gc.cnts[i * YBG_MAX_AGGS + g] = 0;
       gc.vals_hi[i * YBG_MAX_AGGS + g] = 0;
       gc.poison[i * YBG_MAX_AGGS + g] = 0;
@@ -413,14 +392,12 @@ __global__ __launch_bounds__(kThreads, WPS) void k_group(
     gh.hit = 0;
     bool walked_next = false;
     if (active) {
-      const uint64_t lo = j * ivb;
-      uint64_t hi = lo + ivb;
-      if (hi > n_ivs) hi = n_ivs;
+      uint64_t lo, hi;
+      batch_bounds(nullptr, j, ivb, n_ivs, &lo, &hi);
       if (!scan_one_interval<NA, false, true>(
-              sp, data, block_offsets, ivs, n_ivs, lo, aux, key, rk_save,
+              sp, data, block_offsets, ivs, n_ivs, lo, hi, aux, key, rk_save,
               bht, &entries, &scanned, &matched, agg_val, agg_cnt, &ho,
-              &walked_next, nullptr, nullptr, nullptr, &gc, nullptr, &gh,
-              hi)) {
+              &walked_next, nullptr, nullptr, nullptr, nullptr, &gc, &gh)) {
         atomicAdd(err_counter, 1ull);
       }
     }
@@ -456,20 +433,7 @@ __global__ __launch_bounds__(kThreads, WPS) void k_group(
   // group scans report GetReadRestartData like plain scans)
   if (sp.track_restart && (threadIdx.x & 63) == 0) {
     uint64_t wave_id = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
-    uint64_t mh = 0, ml = 0, mn = 0;
-    for (int l = 0; l < 64; ++l) {
-      const uint64_t* rr = bht_scratch + (size_t)(threadIdx.x + l) * 6 + 3;
-      if (rr[2] == 0) continue;
-      if (mn == 0 || u128_slice_cmp(rr[0], rr[1], (uint32_t)rr[2], mh, ml,
-                                    (uint32_t)mn) < 0) {
-        mh = rr[0];
-        ml = rr[1];
-        mn = rr[2];
-      }
-    }
-    partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS] = mh;
-    partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 1] = ml;
-    partials[wave_id * kPartialStride + 4 + 2 * YBG_MAX_AGGS + 2] = mn;
+    wave_restart_min(bht_scratch, 6, 3, partials + wave_id * kPartialStride);
   }
 }
 
@@ -1659,13 +1623,8 @@ int scan_flags_stats(ybg_scan_t* s, const DevSpec& d, ScanStats* out) {
   out->entries = r.entries;
   out->scanned = r.scanned;
   out->errs = r.errs;
-  uint32_t n = (uint32_t)r.restart_len;
-  if (n > YBG_MAX_HT) n = YBG_MAX_HT;
-  for (uint32_t i = 0; i < n; ++i)
-    out->restart_ht[i] = (uint8_t)(
-        (i < 8 ? r.restart_hi >> (56 - 8 * i)
-               : r.restart_lo >> (56 - 8 * (i - 8))) & 0xff);
-  out->restart_len = n;
+  out->restart_len = unpack_restart_ht(r.restart_hi, r.restart_lo,
+                                       r.restart_len, out->restart_ht);
   return 0;
 }
 
@@ -1747,16 +1706,6 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
       s->d_partials + s->n_partials * kPartialStride, 0,
       s->n_partials * kPartialStride * sizeof(uint64_t), s->stream));
   HIP_TRY(hipEventRecord(s->ev_start, s->stream));
-  // dispatch on aggregate-slot capacity (register footprint) and the
-  // waves-per-SIMD occupancy bound (YBG_WPS for tuning; default 3
-  // measured for the 2-agg shape — the 4-agg kernel at 3 waves carries
-  // 240 B/lane of scratch spills vs 0 at 2 waves, so it defaults to 2;
-  // the 8-agg kernel spills either way and keeps 3)
-  int wps = s->na_cap == 4 ? 2 : 3;
-  if (const char* e = getenv("YBG_WPS")) {
-    long v = atol(e);
-    if (v >= 2 && v <= 6) wps = (int)v;
-  }
   HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_spec), &s->dspec,
                                  sizeof(DevSpec), 0, hipMemcpyHostToDevice,
                                  s->stream));
@@ -1781,38 +1730,20 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
                          s->d_partials, s->d_heads, s->d_walked, s->ivb,
                          n_bat, bat_lo, s->d_retry, s->d_retry_n);
     };
-    int fwps = wps;
-    if (const char* e = getenv("YBG_FWPS")) {
-      long v = atol(e);
-      if (v >= 2 && v <= 8) fwps = (int)v;
-    }
     // NC: compile-time column cap for the unrolled load pass (spec is
     // zero-padded up to it; fast_eligible caps num_value_cols at 8).
     // fuse: version-chain decode shape per the spec's expect_versions
-    // hint (instantiated for the default wave count only).
+    // hint. 3 waves/SIMD is the measured optimum.
     const bool nc4 = s->dspec.num_value_cols <= 4;
     bool fuse = s->dspec.fuse_hint != 0;
     if (const char* e = getenv("YBG_FUSE")) fuse = atoi(e) != 0;
-#define YBG_LAUNCH_FAST(W) \
-  do { \
-    if (nc4) launchf(k_scan_fast<W, 4>); \
-    else launchf(k_scan_fast<W, 8>); \
-  } while (0)
-    switch (fwps) {
-      case 2: YBG_LAUNCH_FAST(2); break;
-      case 4: YBG_LAUNCH_FAST(4); break;
-      case 5: YBG_LAUNCH_FAST(5); break;
-      case 6: YBG_LAUNCH_FAST(6); break;
-      default:
-        if (fuse) {
-          if (nc4) launchf(k_scan_fast<3, 4, true>);
-          else launchf(k_scan_fast<3, 8, true>);
-        } else {
-          YBG_LAUNCH_FAST(3);
-        }
-        break;
+    if (fuse) {
+      if (nc4) launchf(k_scan_fast<3, 4, true>);
+      else launchf(k_scan_fast<3, 8, true>);
+    } else {
+      if (nc4) launchf(k_scan_fast<3, 4>);
+      else launchf(k_scan_fast<3, 8>);
     }
-#undef YBG_LAUNCH_FAST
     // retry pass: the general kernel over the aborted batch list, into
     // the second partials half
     int rg = std::min(s->grid, 1024);
@@ -1832,23 +1763,14 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
                          (const uint64_t*)nullptr,
                          (const unsigned long long*)nullptr);
     };
-    switch (na * 10 + wps) {
-      case 22: launch(k_scan<2, 2>); break;
-      case 23: launch(k_scan<2, 3>); break;
-      case 25: launch(k_scan<2, 5>); break;
-      case 26: launch(k_scan<2, 6>); break;
-      case 42: launch(k_scan<4, 2>); break;
-      case 43: launch(k_scan<4, 3>); break;
-      case 45: launch(k_scan<4, 5>); break;
-      case 46: launch(k_scan<4, 6>); break;
-      case 82: launch(k_scan<8, 2>); break;
-      case 83: launch(k_scan<8, 3>); break;
-      case 85: launch(k_scan<8, 5>); break;
-      case 86: launch(k_scan<8, 6>); break;
-      case 44: launch(k_scan<4, 4>); break;
-      case 84: launch(k_scan<8, 4>); break;
-      default: launch(k_scan<2, 4>); break;
-    }
+    // dispatch on aggregate-slot capacity (register footprint), each at
+    // its measured waves-per-SIMD bound: 3 for the 2-agg shape; the 4-agg
+    // kernel at 3 waves carries 240 B/lane of scratch spills vs 0 at 2
+    // waves, so it runs at 2; the 8-agg kernel spills either way and
+    // keeps 3
+    if (na == 2) launch(k_scan<2, 3>);
+    else if (na == 4) launch(k_scan<4, 2>);
+    else launch(k_scan<8, 3>);
   }
   HIP_TRY(hipEventRecord(s->ev_mid, s->stream));
   hipLaunchKernelGGL(k_reduce_pre, dim3(1024), dim3(256), 0, s->stream,
@@ -1899,15 +1821,8 @@ int yb_gpu_scan_aggregate(ybg_scan_t* s, ybg_scan_result_t* out) {
   out->entries_seen = r.entries;
   out->rows_scanned = r.scanned;
   out->rows_matched = r.matched;
-  if (r.restart_len) {
-    uint32_t n = (uint32_t)r.restart_len;
-    if (n > YBG_MAX_HT) n = YBG_MAX_HT;
-    for (uint32_t i = 0; i < n; ++i)
-      out->restart_ht[i] = (uint8_t)(
-          (i < 8 ? r.restart_hi >> (56 - 8 * i)
-                 : r.restart_lo >> (56 - 8 * (i - 8))) & 0xff);
-    out->restart_ht_len = n;
-  }
+  out->restart_ht_len = unpack_restart_ht(r.restart_hi, r.restart_lo,
+                                          r.restart_len, out->restart_ht);
   for (int g = 0; g < s->spec.num_aggs; ++g) {
     ybg_agg_result_t& a = out->aggs[g];
     a.is_null = (r.agg_cnt[g] == 0);
@@ -2048,11 +1963,6 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t* s, uint64_t* keys,
                            s->n_partials * kPartialStride * sizeof(uint64_t),
                            s->stream));
   }
-  int gwps = 3;
-  if (const char* e = getenv("YBG_GWPS")) {
-    long v = atol(e);
-    if (v == 2 || v == 3) gwps = (int)v;
-  }
   auto launch_group = [&](auto kern, auto kern_heads) {
     hipLaunchKernelGGL(kern, dim3(s->grid), dim3(kThreads), 0,
                        s->stream, s->d_data, s->d_offsets, s->d_ivs,
@@ -2063,13 +1973,9 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t* s, uint64_t* keys,
                        s->n_gheads);
   };
   if (s->dspec.num_aggs <= 4) {
-    auto kh = k_group_heads<4>;
-    if (gwps == 2) launch_group(k_group<4, 2>, kh);
-    else launch_group(k_group<4, 3>, kh);
+    launch_group(k_group<4, 3>, k_group_heads<4>);
   } else {
-    auto kh = k_group_heads<8>;
-    if (gwps == 2) launch_group(k_group<8, 2>, kh);
-    else launch_group(k_group<8, 3>, kh);
+    launch_group(k_group<8, 3>, k_group_heads<8>);
   }
   if (s->dspec.track_restart) {
     // fold the wave restart minima into DevResult (num_aggs = 0 spec: only
@@ -2142,13 +2048,8 @@ int yb_gpu_scan_restart_data(ybg_scan_t* s, uint8_t* ht_out,
   HIP_TRY(hipStreamSynchronize(s->stream));
   DevResult r;
   HIP_TRY(hipMemcpy(&r, s->d_result, sizeof(r), hipMemcpyDeviceToHost));
-  uint32_t n = (uint32_t)r.restart_len;
-  if (n > YBG_MAX_HT) n = YBG_MAX_HT;
-  for (uint32_t i = 0; i < n; ++i)
-    ht_out[i] = (uint8_t)((i < 8 ? r.restart_hi >> (56 - 8 * i)
-                                 : r.restart_lo >> (56 - 8 * (i - 8))) &
-                          0xff);
-  *len_out = n;
+  *len_out = unpack_restart_ht(r.restart_hi, r.restart_lo, r.restart_len,
+                               ht_out);
   return 0;
 }
 

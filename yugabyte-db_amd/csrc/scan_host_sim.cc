@@ -29,23 +29,11 @@ uint64_t sim_ivb() {
   }
   return 1;
 }
-}  // namespace
 
-extern "C" {
-
-// Mirrors yb_gpu_scan_open's spec translation + k_scan + k_reduce, serially.
-int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
-                 const uint64_t* offsets, uint64_t n_blocks,
-                 ybg_scan_result_t* out) {
-  // ---- DevSpec from ABI spec (shared translation) ----
-  DevSpec d;
-  std::vector<unsigned char> aux(1 << 20);
-  uint32_t aux_len = 0;
-  build_dev_spec(spec, &d, aux.data(), &aux_len, (uint32_t)aux.size());
-  aux.resize(aux_len + 16, 0);  // windowed-load tail slack (see ABI open)
-
-  // ---- interval table (k_count_restarts + k_emit_intervals, serial) ----
-  std::vector<Interval> ivs;
+// Interval table from the blocks' restart arrays (k_count_restarts +
+// k_emit_intervals, serial). Returns 3 on a malformed block.
+int build_intervals(const uint8_t* data, const uint64_t* offsets,
+                    uint64_t n_blocks, std::vector<Interval>* ivs) {
   for (uint64_t b = 0; b < n_blocks; ++b) {
     uint64_t sz = offsets[b + 1] - offsets[b];
     if (sz < 8) return 3;
@@ -58,9 +46,65 @@ int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
       uint32_t end = (r + 1 < nr)
                          ? load_le32_u(blk + restarts_off + 4ull * (r + 1))
                          : restarts_off;
-      ivs.push_back(Interval{(uint32_t)b, start, end});
+      ivs->push_back(Interval{(uint32_t)b, start, end});
     }
   }
+  return 0;
+}
+
+// DevSpec + aux bytes from the ABI spec (the translation yb_gpu_scan_open
+// uses), with the same 16 bytes of windowed-load tail slack.
+void build_spec(const ybg_scan_spec_t* spec, DevSpec* d,
+                std::vector<unsigned char>* aux) {
+  aux->assign(1 << 20, 0);
+  uint32_t aux_len = 0;
+  build_dev_spec(spec, d, aux->data(), &aux_len, (uint32_t)aux->size());
+  aux->resize(aux_len + 16, 0);
+}
+
+// Counters, aggregates and the restart-min slot bht[3..5] = {hi, lo, len}
+// (process_entry tracking) into the ABI result.
+void store_result(const DevSpec& d, uint64_t entries, uint64_t scanned,
+                  uint64_t matched, const uint64_t* agg_val,
+                  const uint64_t* agg_cnt, const uint64_t* bht,
+                  ybg_scan_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  out->entries_seen = entries;
+  out->rows_scanned = scanned;
+  out->rows_matched = matched;
+  out->restart_ht_len =
+      unpack_restart_ht(bht[3], bht[4], bht[5], out->restart_ht);
+  for (int g = 0; g < d.num_aggs; ++g) {
+    out->aggs[g].is_null = (agg_cnt[g] == 0);
+    switch (d.aggs[g].op) {
+      case YBG_AGG_SUM_DOUBLE:
+      case YBG_AGG_MIN_DOUBLE:
+      case YBG_AGG_MAX_DOUBLE: {
+        double dd;
+        memcpy(&dd, &agg_val[g], 8);
+        out->aggs[g].value_f64 = dd;
+        break;
+      }
+      default:
+        out->aggs[g].value_i64 = (int64_t)agg_val[g];
+        break;
+    }
+  }
+}
+}  // namespace
+
+extern "C" {
+
+// Mirrors yb_gpu_scan_open's spec translation + k_scan + k_reduce, serially.
+int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
+                 const uint64_t* offsets, uint64_t n_blocks,
+                 ybg_scan_result_t* out) {
+  DevSpec d;
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
+
+  std::vector<Interval> ivs;
+  if (int rc = build_intervals(data, offsets, n_blocks, &ivs)) return rc;
   uint64_t n_ivs = ivs.size();
 
   // ---- per-batch scan (k_scan body, serial) ----
@@ -79,11 +123,9 @@ int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
     uint64_t lo = b * ivb;
     uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
     if (!scan_one_interval<YBG_MAX_AGGS>(d, data, offsets, ivs.data(), n_ivs,
-                                         lo, aux.data(), key, rk_save, bht,
-                                         &e32, &s32, &m32,
-                                         agg_val, agg_cnt, &heads[b], &wn,
-                                         nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, hi))
+                                         lo, hi, aux.data(), key, rk_save,
+                                         bht, &e32, &s32, &m32, agg_val,
+                                         agg_cnt, &heads[b], &wn, nullptr))
       return 6;
     entries += e32;
     scanned += s32;
@@ -99,35 +141,7 @@ int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
     agg_combine(d, agg_val, agg_cnt, heads[b].val, heads[b].cnt);
   }
 
-  memset(out, 0, sizeof(*out));
-  out->entries_seen = entries;
-  out->rows_scanned = scanned;
-  out->rows_matched = matched;
-  if (bht[5]) {  // restart-min slot {hi, lo, len} (process_entry tracking)
-    uint32_t n = (uint32_t)bht[5];
-    if (n > YBG_MAX_HT) n = YBG_MAX_HT;
-    for (uint32_t i = 0; i < n; ++i)
-      out->restart_ht[i] = (uint8_t)(
-          (i < 8 ? bht[3] >> (56 - 8 * i) : bht[4] >> (56 - 8 * (i - 8))) &
-          0xff);
-    out->restart_ht_len = n;
-  }
-  for (int g = 0; g < d.num_aggs; ++g) {
-    out->aggs[g].is_null = (agg_cnt[g] == 0);
-    switch (d.aggs[g].op) {
-      case YBG_AGG_SUM_DOUBLE:
-      case YBG_AGG_MIN_DOUBLE:
-      case YBG_AGG_MAX_DOUBLE: {
-        double dd;
-        memcpy(&dd, &agg_val[g], 8);
-        out->aggs[g].value_f64 = dd;
-        break;
-      }
-      default:
-        out->aggs[g].value_i64 = (int64_t)agg_val[g];
-        break;
-    }
-  }
+  store_result(d, entries, scanned, matched, agg_val, agg_cnt, bht, out);
   return 0;
 }
 
@@ -139,28 +153,12 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
                       const uint64_t* offsets, uint64_t n_blocks,
                       ybg_scan_result_t* out, uint64_t* n_fallback_out) {
   DevSpec d;
-  std::vector<unsigned char> aux(1 << 20);
-  uint32_t aux_len = 0;
-  build_dev_spec(spec, &d, aux.data(), &aux_len, (uint32_t)aux.size());
-  aux.resize(aux_len + 16, 0);
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
   if (!fast_eligible(d)) return 9;
 
   std::vector<Interval> ivs;
-  for (uint64_t b = 0; b < n_blocks; ++b) {
-    uint64_t sz = offsets[b + 1] - offsets[b];
-    if (sz < 8) return 3;
-    const uint8_t* blk = data + offsets[b];
-    uint32_t nr = load_le32_u(blk + sz - 4);
-    if (nr == 0 || (uint64_t)nr * 4 + 4 > sz) return 3;
-    uint32_t restarts_off = (uint32_t)(sz - 4 - (uint64_t)nr * 4);
-    for (uint32_t r = 0; r < nr; ++r) {
-      uint32_t start = load_le32_u(blk + restarts_off + 4ull * r);
-      uint32_t end = (r + 1 < nr)
-                         ? load_le32_u(blk + restarts_off + 4ull * (r + 1))
-                         : restarts_off;
-      ivs.push_back(Interval{(uint32_t)b, start, end});
-    }
-  }
+  if (int rc = build_intervals(data, offsets, n_blocks, &ivs)) return rc;
   uint64_t n_ivs = ivs.size();
   const uint64_t ivb = sim_ivb();
   const uint64_t n_b = (n_ivs + ivb - 1) / ivb;
@@ -198,9 +196,8 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
       HeadOut<YBG_MAX_AGGS> ho8;
       e32 = s32 = m32 = 0;
       if (!scan_one_interval<YBG_MAX_AGGS>(
-              d, data, offsets, ivs.data(), n_ivs, lo, aux.data(), key,
-              rk_save, bht, &e32, &s32, &m32, av8, ac8, &ho8, &wn, nullptr,
-              nullptr, nullptr, nullptr, nullptr, nullptr, hi))
+              d, data, offsets, ivs.data(), n_ivs, lo, hi, aux.data(), key,
+              rk_save, bht, &e32, &s32, &m32, av8, ac8, &ho8, &wn, nullptr))
         return 6;
       for (int g = 0; g < 2; ++g) {
         combine1(d.agg_op[g], &agg_val[g], &agg_cnt[g], av8[g], ac8[g]);
@@ -224,35 +221,7 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
       combine1(d.agg_op[g], &agg_val[g], &agg_cnt[g], heads[b].val[g],
                heads[b].cnt[g]);
   }
-  memset(out, 0, sizeof(*out));
-  out->entries_seen = entries;
-  out->rows_scanned = scanned;
-  out->rows_matched = matched;
-  if (bht[5]) {
-    uint32_t n = (uint32_t)bht[5];
-    if (n > YBG_MAX_HT) n = YBG_MAX_HT;
-    for (uint32_t i = 0; i < n; ++i)
-      out->restart_ht[i] = (uint8_t)(
-          (i < 8 ? bht[3] >> (56 - 8 * i) : bht[4] >> (56 - 8 * (i - 8))) &
-          0xff);
-    out->restart_ht_len = n;
-  }
-  for (int g = 0; g < d.num_aggs; ++g) {
-    out->aggs[g].is_null = (agg_cnt[g] == 0);
-    switch (d.aggs[g].op) {
-      case YBG_AGG_SUM_DOUBLE:
-      case YBG_AGG_MIN_DOUBLE:
-      case YBG_AGG_MAX_DOUBLE: {
-        double dd;
-        memcpy(&dd, &agg_val[g], 8);
-        out->aggs[g].value_f64 = dd;
-        break;
-      }
-      default:
-        out->aggs[g].value_i64 = (int64_t)agg_val[g];
-        break;
-    }
-  }
+  store_result(d, entries, scanned, matched, agg_val, agg_cnt, bht, out);
   if (n_fallback_out) *n_fallback_out = fallbacks;
   return 0;
 }
@@ -267,28 +236,13 @@ int ybg_sim_emit(const ybg_scan_spec_t* spec, const uint8_t* data,
                  uint64_t* varlen_out) {
   std::vector<uint16_t> hashes(row_cap);
   DevSpec d;
-  std::vector<unsigned char> aux(1 << 20);
-  uint32_t aux_len = 0;
+  std::vector<unsigned char> aux;
   ybg_scan_spec_t spec2 = *spec;
   spec2.emit_rows = 1;
-  build_dev_spec(&spec2, &d, aux.data(), &aux_len, (uint32_t)aux.size());
+  build_spec(&spec2, &d, &aux);
 
   std::vector<Interval> ivs;
-  for (uint64_t b = 0; b < n_blocks; ++b) {
-    uint64_t sz = offsets[b + 1] - offsets[b];
-    if (sz < 8) return 3;
-    const uint8_t* blk = data + offsets[b];
-    uint32_t nr = load_le32_u(blk + sz - 4);
-    if (nr == 0 || (uint64_t)nr * 4 + 4 > sz) return 3;
-    uint32_t restarts_off = (uint32_t)(sz - 4 - (uint64_t)nr * 4);
-    for (uint32_t r = 0; r < nr; ++r) {
-      uint32_t start = load_le32_u(blk + restarts_off + 4ull * r);
-      uint32_t end = (r + 1 < nr)
-                         ? load_le32_u(blk + restarts_off + 4ull * (r + 1))
-                         : restarts_off;
-      ivs.push_back(Interval{(uint32_t)b, start, end});
-    }
-  }
+  if (int rc = build_intervals(data, offsets, n_blocks, &ivs)) return rc;
   uint64_t n_ivs = ivs.size();
   const uint64_t ivb = sim_ivb();
   const uint64_t n_b = (n_ivs + ivb - 1) / ivb;
@@ -306,11 +260,9 @@ int ybg_sim_emit(const ybg_scan_spec_t* spec, const uint8_t* data,
     uint64_t lo = b * ivb;
     uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
     if (!scan_one_interval<YBG_MAX_AGGS>(d, data, offsets, ivs.data(), n_ivs,
-                                         lo, aux.data(), key, rk_save, bht,
-                                         &entries, &scanned, &matched,
+                                         lo, hi, aux.data(), key, rk_save,
+                                         bht, &entries, &scanned, &matched,
                                          agg_val, agg_cnt, &ho, &wn,
-                                         nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, hi,
                                          head_consumed.data()))
       return 6;
   }
@@ -337,9 +289,9 @@ int ybg_sim_emit(const ybg_scan_spec_t* spec, const uint8_t* data,
     bool wn = false;
     HeadOut<YBG_MAX_AGGS> ho2;
     if (!scan_one_interval<YBG_MAX_AGGS, true>(
-            d, data, offsets, ivs.data(), n_ivs, j, aux.data(), key, rk_save,
-            bht, &entries, &scanned, &matched, agg_val, agg_cnt, &ho2, &wn,
-            &ec, rowbuf, lenbuf))
+            d, data, offsets, ivs.data(), n_ivs, j, j + 1, aux.data(), key,
+            rk_save, bht, &entries, &scanned, &matched, agg_val, agg_cnt,
+            &ho2, &wn, nullptr, &ec, rowbuf, lenbuf))
       return 6;
   }
   if (overflow) return 8;
@@ -357,27 +309,12 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
                   uint64_t key_bytes_cap, uint64_t cap, uint64_t* n_out,
                   uint8_t* restart_out, uint32_t* restart_len_out) {
   DevSpec d;
-  std::vector<unsigned char> aux(1 << 20);
-  uint32_t aux_len = 0;
-  build_dev_spec(spec, &d, aux.data(), &aux_len, (uint32_t)aux.size());
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
   if (d.group_col < 0) return 9;
 
   std::vector<Interval> ivs;
-  for (uint64_t b = 0; b < n_blocks; ++b) {
-    uint64_t sz = offsets[b + 1] - offsets[b];
-    if (sz < 8) return 3;
-    const uint8_t* blk = data + offsets[b];
-    uint32_t nr = load_le32_u(blk + sz - 4);
-    if (nr == 0 || (uint64_t)nr * 4 + 4 > sz) return 3;
-    uint32_t restarts_off = (uint32_t)(sz - 4 - (uint64_t)nr * 4);
-    for (uint32_t r = 0; r < nr; ++r) {
-      uint32_t start = load_le32_u(blk + restarts_off + 4ull * r);
-      uint32_t end = (r + 1 < nr)
-                         ? load_le32_u(blk + restarts_off + 4ull * (r + 1))
-                         : restarts_off;
-      ivs.push_back(Interval{(uint32_t)b, start, end});
-    }
-  }
+  if (int rc = build_intervals(data, offsets, n_blocks, &ivs)) return rc;
   uint64_t n_ivs = ivs.size();
   const uint64_t ivb = sim_ivb();
   const uint64_t n_b = (n_ivs + ivb - 1) / ivb;
@@ -397,16 +334,8 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
   std::vector<unsigned long long> vals_hi((gcap + 1) * YBG_MAX_AGGS, 0);
   std::vector<unsigned> poison((gcap + 1) * YBG_MAX_AGGS, 0);
   for (uint64_t i = 0; i <= gcap; ++i)
-    for (int g = 0; g < d.num_aggs; ++g) {
-      if (d.aggs[g].op == YBG_AGG_MIN_INT64)
-        vals[i * YBG_MAX_AGGS + g] = 0x7fffffffffffffffll;
-      else if (d.aggs[g].op == YBG_AGG_MAX_INT64)
-        vals[i * YBG_MAX_AGGS + g] = (long long)0x8000000000000000ll;
-      else if (d.aggs[g].op == YBG_AGG_MIN_DOUBLE)
-        vals[i * YBG_MAX_AGGS + g] = (long long)~0ull;
-      else if (d.aggs[g].op == YBG_AGG_MAX_DOUBLE)
-        vals[i * YBG_MAX_AGGS + g] = 0;
-    }
+    for (int g = 0; g < d.num_aggs; ++g)
+      vals[i * YBG_MAX_AGGS + g] = group_init_value(d.aggs[g].op);
   unsigned long long overflow = 0;
   GroupCtx gc;
   gc.gkey = gkey.data();
@@ -425,9 +354,9 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
     uint64_t lo = b * ivb;
     uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
     if (!scan_one_interval<YBG_MAX_AGGS, false, true>(
-            d, data, offsets, ivs.data(), n_ivs, lo, aux.data(), key, rk_save,
-            bht, &entries, &scanned, &matched, agg_val, agg_cnt, &ho, &wn,
-            nullptr, nullptr, nullptr, &gc, nullptr, &gheads[b], hi))
+            d, data, offsets, ivs.data(), n_ivs, lo, hi, aux.data(), key,
+            rk_save, bht, &entries, &scanned, &matched, agg_val, agg_cnt, &ho,
+            &wn, nullptr, nullptr, nullptr, nullptr, &gc, &gheads[b]))
       return 6;
     walked[b] = wn ? 1 : 0;
   }
@@ -440,15 +369,9 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
   if (overflow) return 8;
   if (restart_len_out) {  // restart-min slot, as ybg_sim_scan reports it
     *restart_len_out = 0;
-    if (bht[5] && restart_out) {
-      uint32_t rn = (uint32_t)bht[5];
-      if (rn > YBG_MAX_HT) rn = YBG_MAX_HT;
-      for (uint32_t i = 0; i < rn; ++i)
-        restart_out[i] = (uint8_t)(
-            (i < 8 ? bht[3] >> (56 - 8 * i) : bht[4] >> (56 - 8 * (i - 8))) &
-            0xff);
-      *restart_len_out = rn;
-    }
+    if (restart_out)
+      *restart_len_out =
+          unpack_restart_ht(bht[3], bht[4], bht[5], restart_out);
   }
   bool grp_is_str =
       d.cols[d.group_col].dtype == YBG_T_STRING;
