@@ -65,6 +65,11 @@ def _lib():
     lib.yb_gpu_snapshot_query.argtypes = [C.c_void_p,
                                           C.POINTER(y.SnapshotQuery),
                                           C.POINTER(y.ScanResult)]
+    lib.yb_gpu_snapshot_group_query.restype = C.c_int
+    lib.yb_gpu_snapshot_group_query.argtypes = [
+        C.c_void_p, C.POINTER(y.SnapshotGroupQuery), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64,
+        C.POINTER(y.SnapshotGroupResult)]
     lib.yb_gpu_snapshot_kernel_ms.restype = C.c_int
     lib.yb_gpu_snapshot_kernel_ms.argtypes = [C.c_void_p,
                                               C.POINTER(C.c_double)]
@@ -259,6 +264,46 @@ class GpuSnapshot:
             self._lib.yb_gpu_snapshot_query(self._h, C.byref(q),
                                             C.byref(res)), "snapshot_query")
         return res
+
+    def group_query_raw(self, preds, aggs, group_col, group_is_key=False,
+                        expect_groups=0, cap=1 << 20):
+        """GROUP BY on the snapshot (yb_gpu_snapshot_group_query): raw
+        ctypes arrays (keys, vals, cnts) plus the SnapshotGroupResult. The
+        first result.n_groups entries are written: ascending by key as an
+        unsigned 64-bit pattern, the NULL group (result.has_null_group)
+        last. Output buffers are allocated once per capacity and reused,
+        like GpuScan.group_aggregate_raw's. Errors raise GpuScanError with
+        .code (9 unsupported query, 8 cap too small) and .result."""
+        gb = getattr(self, "_group_bufs", None)
+        if gb is None or gb[0] != cap:
+            n = max(cap, 1)
+            gb = (cap, (C.c_uint64 * n)(), (C.c_int64 * (n * y.MAX_AGGS))(),
+                  (C.c_uint64 * (n * y.MAX_AGGS))())
+            self._group_bufs = gb
+        keys, vals, cnts = gb[1], gb[2], gb[3]
+        q = y.snapshot_group_query(preds, aggs, group_col, group_is_key,
+                                   expect_groups)
+        res = y.SnapshotGroupResult()
+        rc = self._lib.yb_gpu_snapshot_group_query(
+            self._h, C.byref(q), keys, vals, cnts, cap, C.byref(res))
+        if rc:
+            err = GpuScanError(
+                f"snapshot_group_query rc={rc}: "
+                f"{self._lib.yb_gpu_last_error().decode()}")
+            err.code = rc
+            err.result = res
+            raise err
+        return keys, vals, cnts, res
+
+    def group_query(self, preds, aggs, group_col, group_is_key=False,
+                    expect_groups=0, cap=1 << 20):
+        """GROUP BY on the snapshot: {key: (aggs...)} in the shape of
+        GpuScan.group_aggregate, None keying the NULL group. expect_groups
+        is a hint (0 = unknown) that picks the kernel level, never the
+        result."""
+        keys, vals, cnts, res = self.group_query_raw(
+            preds, aggs, group_col, group_is_key, expect_groups, cap)
+        return y.decode_snapshot_groups(res, keys, vals, cnts, list(aggs))
 
     def kernel_ms(self):
         ms = C.c_double()

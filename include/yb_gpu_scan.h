@@ -267,7 +267,8 @@ int yb_gpu_scan_aggregate(ybg_scan_t *s, ybg_scan_result_t *out);
 
 /* GROUP BY (spec.group_col >= 0): run the grouped scan and return the
  * per-group partials. keys[g]: numeric group key datum, or for string group
- * columns (len<<40)|offset into key_bytes. vals/cnts: [n_groups * num_aggs]
+ * columns (len<<40)|offset into key_bytes. vals/cnts:
+ * [n_groups * YBG_MAX_AGGS], aggregate g of group i at i * YBG_MAX_AGGS + g
  * (value bit pattern + non-null contribution count; cnt==0 <=> NULL).
  * Returns 0 and *n_groups on success; error if cap exceeded. Integer
  * aggregates are exact; grouped double SUM uses device atomics and is only
@@ -429,6 +430,70 @@ typedef struct {
  * separately built snapshots of the same tablet. */
 int yb_gpu_snapshot_query(ybg_snapshot_t *sn, const ybg_snapshot_query_t *q,
                           ybg_scan_result_t *out);
+/* GROUP BY on a snapshot: predicates as for yb_gpu_snapshot_query, 1 to
+ * YBG_MAX_AGGS aggregates (all eight ops), one group column — any staged
+ * value column or staged key column (every numeric column: int64, int32,
+ * double, bool). */
+typedef struct {
+  int32_t num_preds; ybg_pred_t preds[YBG_MAX_PREDS];
+  int32_t num_aggs;  ybg_agg_t  aggs[YBG_MAX_AGGS];
+  int32_t group_is_key_col;   /* like ybg_pred_t.is_key_col */
+  int32_t group_col;          /* like ybg_pred_t.col */
+  uint64_t expect_groups;     /* hint; 0 = unknown */
+} ybg_snapshot_group_query_t;
+
+typedef struct {
+  uint64_t n_groups;          /* incl. the NULL-key group */
+  uint64_t rows_scanned, rows_matched, entries_seen;
+  int32_t  has_null_group;    /* 1: LAST entry is the NULL-key group, keys[] = 0 */
+  int32_t  local_level;       /* 1: the LDS-level kernel ran, 0: global-only */
+  uint8_t  restart_ht[YBG_MAX_HT]; uint32_t restart_ht_len;  /* the build's */
+} ybg_snapshot_group_result_t;
+
+/* Synchronous. keys: [cap]; vals / cnts: [cap * YBG_MAX_AGGS].
+ * Layout: entry i holds keys[i] and vals / cnts[i * YBG_MAX_AGGS + g] for
+ *   aggregate g: value bit pattern + contribution count, cnt == 0 <=> NULL;
+ *   columns past num_aggs are written as zero.
+ * Order: ascending by the group key datum taken as an UNSIGNED 64-bit
+ *   pattern (the bit pattern yb_gpu_scan_next_batch delivers for the
+ *   column). This is a canonical order, not SQL order: negative integers
+ *   and doubles do not sort numerically.
+ * NULL group: rows whose group-column value is NULL (key columns are never
+ *   NULL) form one group; if present it is the LAST entry, its keys[] is 0
+ *   and out->has_null_group is 1 — it cannot be mistaken for any key value
+ *   (a tablet holding both key -1 and NULL keys yields two groups).
+ * Determinism: keys, vals and cnts are byte-identical across repeated
+ *   queries, across separately built snapshots of the same tablet, and
+ *   whichever kernel level ran. Double SUM accumulates as 128-bit 2^-60
+ *   fixed point, so it is exact in any order; a non-finite operand or one
+ *   outside +-2^66 poisons that group's sum to NaN (the block path's rule).
+ * Levels: with expect_groups <= ybg_snapshot_group_local_slots(num_aggs)
+ *   (0 = unknown included) rows are first aggregated in a workgroup-local
+ *   LDS table that is flushed once into the global table; a larger hint
+ *   sends every row straight to the global table. The hint never changes
+ *   the result; out->local_level reports the level that ran.
+ * Semantics: NULL handling is yb_gpu_snapshot_query's. An empty snapshot or
+ *   a query no row matches returns n_groups == 0 (n_rows == 0 launches
+ *   nothing).
+ * Errors: 9, naming the offender, launching nothing and leaving the
+ *   snapshot usable, for everything yb_gpu_snapshot_query rejects, a string
+ *   or out-of-range group column, and num_aggs == 0. 8 when cap is smaller
+ *   than the group count (out->n_groups then holds the count needed) or the
+ *   group table overflows. 10 device.
+ * Memory: the first grouped query allocates the snapshot's group table
+ *   (capacity = the smallest power of two >= 2 * n_rows, clamped to
+ *   [1024, 2^20]) and its export scratch; ybg_snapshot_info_t.device_bytes
+ *   includes them from then on.
+ * yb_gpu_snapshot_kernel_ms then reports table init + query + export. */
+int yb_gpu_snapshot_group_query(ybg_snapshot_t *sn,
+                                const ybg_snapshot_group_query_t *q,
+                                uint64_t *keys, int64_t *vals, uint64_t *cnts,
+                                uint64_t cap,
+                                ybg_snapshot_group_result_t *out);
+/* LDS-level slot count of the kernel instantiation a query with num_aggs
+ * aggregates selects (tests derive cardinalities from it). */
+uint64_t ybg_snapshot_group_local_slots(int32_t num_aggs);
+
 /* Device time (events) of the last query: query kernel + final reduce. */
 int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t *sn, double *query_ms);
 int yb_gpu_snapshot_close(ybg_snapshot_t *sn);

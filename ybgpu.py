@@ -557,6 +557,104 @@ def sim_snapshot_query(spec, data, offsets, n_blocks, preds, aggs):
     return res
 
 
+class SnapshotGroupQuery(C.Structure):
+    """ybg_snapshot_group_query_t."""
+    _fields_ = [("num_preds", C.c_int32), ("preds", Pred * MAX_PREDS),
+                ("num_aggs", C.c_int32), ("aggs", Agg * MAX_AGGS),
+                ("group_is_key_col", C.c_int32), ("group_col", C.c_int32),
+                ("expect_groups", C.c_uint64)]
+
+
+class SnapshotGroupResult(C.Structure):
+    """ybg_snapshot_group_result_t."""
+    _fields_ = [("n_groups", C.c_uint64), ("rows_scanned", C.c_uint64),
+                ("rows_matched", C.c_uint64), ("entries_seen", C.c_uint64),
+                ("has_null_group", C.c_int32), ("local_level", C.c_int32),
+                ("restart_ht", C.c_uint8 * MAX_HT),
+                ("restart_ht_len", C.c_uint32)]
+
+
+def snapshot_group_query(preds, aggs, group_col, group_is_key=False,
+                         expect_groups=0):
+    """Pack a grouped snapshot query (counts over the caps pass through,
+    as in snapshot_query)."""
+    q = SnapshotGroupQuery()
+    q.num_preds = len(preds)
+    for i, p in enumerate(preds[:MAX_PREDS]):
+        q.preds[i] = p
+    q.num_aggs = len(aggs)
+    for i, a in enumerate(aggs[:MAX_AGGS]):
+        q.aggs[i] = a
+    q.group_is_key_col = 1 if group_is_key else 0
+    q.group_col = group_col
+    q.expect_groups = expect_groups
+    return q
+
+
+def snapshot_group_local_slots(num_aggs):
+    """LDS-level slot count of the grouped snapshot kernel a query with
+    num_aggs aggregates selects (ybg_snapshot_group_local_slots)."""
+    f = _sig(product(), "ybg_snapshot_group_local_slots", C.c_uint64,
+             [C.c_int32])
+    return f(num_aggs)
+
+
+def decode_snapshot_groups(res, keys, vals, cnts, aggs):
+    """Grouped snapshot output -> {key: (aggs...)} in the shape of
+    _decode_groups: key None for the NULL group (flagged by the result, so
+    a key of 2**64 - 1 stays a key); doubles decoded from bit patterns."""
+    import struct
+    out = {}
+    n = res.n_groups
+    for g in range(n):
+        k = None if (res.has_null_group and g == n - 1) else keys[g]
+        row = []
+        for a, ag in enumerate(aggs):
+            c = cnts[g * MAX_AGGS + a]
+            v = vals[g * MAX_AGGS + a]
+            if c == 0:
+                row.append(None)
+            elif ag.op in (AGG_SUM_DOUBLE, AGG_MIN_DOUBLE, AGG_MAX_DOUBLE):
+                row.append(struct.unpack("<d", struct.pack("<q", v))[0])
+            else:
+                row.append(v)
+        out[k] = tuple(row)
+    return out
+
+
+def sim_snapshot_group_query(spec, data, offsets, n_blocks, preds, aggs,
+                             group_col, group_is_key=False, expect_groups=0,
+                             cap=1 << 16):
+    """Host SIMULATOR of the grouped snapshot query
+    (ybg_sim_snapshot_group_query) — TEST INFRASTRUCTURE: the snapshot
+    layout built as in sim_snapshot_query, then the device accumulate /
+    flush / export code one simulated workgroup at a time. Returns
+    (groups dict, (keys, vals, cnts) raw ctypes arrays, result struct);
+    raises RuntimeError carrying .code and .result on a non-zero code."""
+    lib = product()
+    f = _sig(lib, "ybg_sim_snapshot_group_query", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64,
+              C.POINTER(SnapshotGroupQuery), C.POINTER(C.c_uint64),
+              C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64,
+              C.POINTER(SnapshotGroupResult)])
+    q = snapshot_group_query(preds, aggs, group_col, group_is_key,
+                             expect_groups)
+    keys = (C.c_uint64 * max(cap, 1))()
+    vals = (C.c_int64 * (max(cap, 1) * MAX_AGGS))()
+    cnts = (C.c_uint64 * (max(cap, 1) * MAX_AGGS))()
+    res = SnapshotGroupResult()
+    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), keys, vals,
+           cnts, cap, C.byref(res))
+    if rc != 0:
+        err = RuntimeError(f"ybg_sim_snapshot_group_query failed rc={rc}")
+        err.code = rc
+        err.result = res
+        raise err
+    groups = decode_snapshot_groups(res, keys, vals, cnts, list(aggs))
+    return groups, (keys, vals, cnts), res
+
+
 def sim_scan_fast(spec, data, offsets, n_blocks):
     """Host simulator of the SPECIALIZED fast batch scanner
     (scan_batch_fast + general fallback per aborted batch) — TEST

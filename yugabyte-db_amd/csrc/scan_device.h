@@ -2234,25 +2234,44 @@ DEV uint64_t f64_unordered(uint64_t u) {
 // order-independent => deterministic run to run and across GPU counts,
 // unlike a float atomic-add. Values outside +-2^66 or non-finite poison
 // the slot (exported as NaN). doc_expr.cc:341-395 semantics otherwise.
-DEV void group_sum_f64_fixed(const GroupCtx& gc, uint64_t slot, int g,
-                             uint64_t dbits) {
+// f64_to_fixed128: the 2^-60 fixed-point image of a double as two's-
+// complement lo/hi words; false (outputs untouched) when the value poisons.
+DEV bool f64_to_fixed128(uint64_t dbits, unsigned long long* lo,
+                         unsigned long long* hi) {
   double v = __longlong_as_double((long long)dbits);
   if (!(v == v) || v > 7.3786976294838206e19 ||
-      v < -7.3786976294838206e19) {
-    ybg_atomic_or_u32(&gc.poison[slot * YBG_MAX_AGGS + g], 1u);
-    return;
-  }
+      v < -7.3786976294838206e19)
+    return false;
   double sc = v * 1152921504606846976.0;  // 2^60
   __int128 f = (__int128)sc;
-  unsigned long long lo = (unsigned long long)(unsigned __int128)f;
-  unsigned long long hi =
-      (unsigned long long)((unsigned __int128)f >> 64);
-  unsigned long long* vlo =
-      (unsigned long long*)&gc.vals[slot * YBG_MAX_AGGS + g];
-  unsigned long long* vhi = &gc.vals_hi[slot * YBG_MAX_AGGS + g];
+  *lo = (unsigned long long)(unsigned __int128)f;
+  *hi = (unsigned long long)((unsigned __int128)f >> 64);
+  return true;
+}
+
+// 128-bit add into a lo/hi word pair, carry taken from the returned old
+// low word (group-table slots, and the snapshot path's LDS-level slots).
+DEV void add_fixed128(unsigned long long* vlo, unsigned long long* vhi,
+                      unsigned long long lo, unsigned long long hi) {
   unsigned long long old = atomicAdd(vlo, lo);
   if (old + lo < old) atomicAdd(vhi, 1ull);
   atomicAdd(vhi, hi);
+}
+
+DEV void group_add_fixed128(const GroupCtx& gc, uint64_t slot, int g,
+                            unsigned long long lo, unsigned long long hi) {
+  add_fixed128((unsigned long long*)&gc.vals[slot * YBG_MAX_AGGS + g],
+               &gc.vals_hi[slot * YBG_MAX_AGGS + g], lo, hi);
+}
+
+DEV void group_sum_f64_fixed(const GroupCtx& gc, uint64_t slot, int g,
+                             uint64_t dbits) {
+  unsigned long long lo, hi;
+  if (!f64_to_fixed128(dbits, &lo, &hi)) {
+    ybg_atomic_or_u32(&gc.poison[slot * YBG_MAX_AGGS + g], 1u);
+    return;
+  }
+  group_add_fixed128(gc, slot, g, lo, hi);
 }
 
 // Final per-slot value decode (shared by the device export kernel and the
@@ -2301,9 +2320,10 @@ struct GroupHead {
 // Accumulate one matching row into its group's table slot. SRC is the live
 // row context (RowCtxT) or a deferred head record (GroupHead: the
 // heads-resolution pass and the in-kernel not-consumed head path); both
-// carry the same grp_* / agg_* field names.
-template <int NA, class SRC>
-DEV void group_accum_from(const DevSpec& sp, const GroupCtx& gc,
+// carry the same grp_* / agg_* field names. SPEC is the DevSpec, or the
+// snapshot path's SnapQuery: anything with num_aggs and aggs[g].op.
+template <int NA, class SRC, class SPEC>
+DEV void group_accum_from(const SPEC& sp, const GroupCtx& gc,
                           const SRC& rc) {
   uint64_t slot;
   if (rc.grp_null) {

@@ -408,15 +408,24 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
   return 0;
 }
 
-// Columnar-snapshot simulator: the build (block scan with predicates and
+}  // extern "C"
+
+namespace {
+// The columnar snapshot's build, serially: block scan with predicates and
 // aggregates stripped -> rows ordered by sort_key -> dense padded column
-// arrays, exactly the device snapshot's layout) followed by the
-// snap_device.h row loop, sequentially. `query` is a ybg_snapshot_query_t.
-// Returns 9 for a query the ABI rejects (same translation code).
-int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
-                           const uint64_t* offsets, uint64_t n_blocks,
-                           const ybg_snapshot_query_t* query,
-                           ybg_scan_result_t* out) {
+// arrays, exactly the device snapshot's layout. `cols` points into the
+// vectors held here.
+struct SimSnapshot {
+  uint64_t n = 0;
+  ybg_scan_result_t stats;
+  std::vector<std::vector<uint64_t>> val, key;
+  std::vector<uint32_t> nullmask;
+  SnapCols cols;
+};
+
+int sim_snapshot_build(const ybg_scan_spec_t* spec, const uint8_t* data,
+                       const uint64_t* offsets, uint64_t n_blocks,
+                       SimSnapshot* sn) {
   ybg_scan_spec_t bs = *spec;
   bs.num_preds = 0;
   bs.num_aggs = 0;
@@ -425,7 +434,7 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
   bs.group_col = 0;
   bs.backward = 0;
   // scan statistics + exact visible-row count (the build's flags pass)
-  ybg_scan_result_t stats;
+  ybg_scan_result_t& stats = sn->stats;
   int rc = ybg_sim_scan(&bs, data, offsets, n_blocks, &stats);
   if (rc) return rc;
   const ybg_schema_t& sc = spec->schema;
@@ -442,6 +451,7 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
                     0, &n, &vl);
   if (rc) return rc;
   if (n != stats.rows_scanned) return 8;
+  sn->n = n;
 
   std::vector<uint32_t> perm(n);
   for (uint64_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
@@ -449,9 +459,13 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
     return sort_key[a] < sort_key[b];
   });
   const uint64_t padded = snap_padded_rows(n);
-  std::vector<std::vector<uint64_t>> val(nc), key(nk);
-  std::vector<uint32_t> nullmask(padded, 0);
-  SnapCols cols;
+  std::vector<std::vector<uint64_t>>& val = sn->val;
+  std::vector<std::vector<uint64_t>>& key = sn->key;
+  std::vector<uint32_t>& nullmask = sn->nullmask;
+  val.resize(nc);
+  key.resize(nk);
+  nullmask.assign(padded, 0);
+  SnapCols& cols = sn->cols;
   memset(&cols, 0, sizeof(cols));
   for (int c = 0; c < nc; ++c) {
     if (sc.value_cols[c].dtype == YBG_T_STRING) continue;
@@ -473,6 +487,27 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
     cols.nullable_cols |= nullmask[r] & nc_mask;
   }
   cols.nullmask = nullmask.data();
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// Columnar-snapshot simulator: the build (sim_snapshot_build) followed by
+// the snap_device.h row loop, sequentially. `query` is a
+// ybg_snapshot_query_t. Returns 9 for a query the ABI rejects (same
+// translation code).
+int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
+                           const uint64_t* offsets, uint64_t n_blocks,
+                           const ybg_snapshot_query_t* query,
+                           ybg_scan_result_t* out) {
+  SimSnapshot snap;
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  if (rc) return rc;
+  const ybg_schema_t& sc = spec->schema;
+  const SnapCols& cols = snap.cols;
+  const uint64_t n = snap.n;
+  const ybg_scan_result_t& stats = snap.stats;
 
   SnapQuery q;
   std::vector<uint8_t> aux;
@@ -512,6 +547,152 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
   }
   snap_fill_result(res, n, stats.entries_seen, stats.restart_ht,
                    stats.restart_ht_len, query->num_aggs, query->aggs, out);
+  return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// k_snap_group_query, one simulated workgroup at a time: workgroup w of
+// snap_grid(n) walks the row pairs the device gives its 256 lanes
+// (grid-stride included) into its own local table, then flushes it.
+template <int NA, bool NULLS, bool GEN, bool LOCAL>
+void sim_group_rows(const SnapGroupQuery& gq, const GroupCtx& gc,
+                    uint64_t* matched) {
+  const SnapQuery& q = gq.q;
+  const uint64_t n = q.n_rows;
+  const uint64_t n_pairs = (n + kSnapVec - 1) / kSnapVec;
+  const uint64_t grid = snap_grid(n);
+  const uint64_t span = grid * kSnapThreads;
+  std::vector<SnapLocalTable<NA>> tab_mem(LOCAL ? 1 : 0);
+  SnapLocalTable<NA>* tab = LOCAL ? tab_mem.data() : nullptr;
+  for (uint64_t w = 0; w < grid; ++w) {
+    if (LOCAL) snap_local_init<NA>(q, tab, 0, 1);
+    for (uint64_t t = 0; t < (uint64_t)kSnapThreads; ++t) {
+      for (uint64_t pi = w * kSnapThreads + t; pi < n_pairs; pi += span) {
+        for (int k = 0; k < kSnapVec; ++k) {
+          const uint64_t r = pi * kSnapVec + k;
+          uint64_t pv[YBG_MAX_PREDS] = {0}, av[NA] = {0};
+          for (int i = 0; i < q.num_preds; ++i) pv[i] = q.preds[i].col[r];
+          for (int g = 0; g < q.num_aggs; ++g)
+            if (q.aggs[g].col) av[g] = q.aggs[g].col[r];
+          snap_group_row<YBG_MAX_PREDS, NA, NULLS, GEN, LOCAL>(
+              gq, pv, av, gq.grp_col[r], NULLS ? q.nullmask[r] : 0u, r < n,
+              matched, tab, gc);
+        }
+      }
+    }
+    if (LOCAL)
+      for (int i = 0; i <= SnapLocalTable<NA>::L; ++i)
+        snap_local_flush_slot<NA>(q, tab, i, gc);
+  }
+}
+
+template <int NA>
+void sim_group_dispatch(const SnapGroupQuery& gq, const GroupCtx& gc,
+                        bool local, uint64_t* matched) {
+  const int v = (gq.q.any_nullable ? 4 : 0) | (gq.q.general ? 2 : 0) |
+                (local ? 1 : 0);
+  switch (v) {
+    case 0: sim_group_rows<NA, false, false, false>(gq, gc, matched); break;
+    case 1: sim_group_rows<NA, false, false, true>(gq, gc, matched); break;
+    case 2: sim_group_rows<NA, false, true, false>(gq, gc, matched); break;
+    case 3: sim_group_rows<NA, false, true, true>(gq, gc, matched); break;
+    case 4: sim_group_rows<NA, true, false, false>(gq, gc, matched); break;
+    case 5: sim_group_rows<NA, true, false, true>(gq, gc, matched); break;
+    case 6: sim_group_rows<NA, true, true, false>(gq, gc, matched); break;
+    default: sim_group_rows<NA, true, true, true>(gq, gc, matched); break;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// Grouped columnar-snapshot simulator: yb_gpu_snapshot_group_query's
+// contract (codes 8 / 9 included) from the same translation, accumulate,
+// flush and export code, serially. The level is chosen from expect_groups
+// like the device dispatch chooses it.
+int ybg_sim_snapshot_group_query(const ybg_scan_spec_t* spec,
+                                 const uint8_t* data, const uint64_t* offsets,
+                                 uint64_t n_blocks,
+                                 const ybg_snapshot_group_query_t* query,
+                                 uint64_t* keys, int64_t* vals,
+                                 uint64_t* cnts, uint64_t cap,
+                                 ybg_snapshot_group_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  SimSnapshot snap;
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  if (rc) return rc;
+  const uint64_t n = snap.n;
+  SnapGroupQuery gq;
+  std::vector<uint8_t> aux;
+  char err[192];
+  rc = snap_build_group_query(spec->schema, &snap.cols, *query, n, &aux, &gq,
+                              err, sizeof(err));
+  if (rc) return rc;
+  gq.q.aux = aux.data();
+  out->rows_scanned = n;
+  out->entries_seen = snap.stats.entries_seen;
+  memcpy(out->restart_ht, snap.stats.restart_ht, snap.stats.restart_ht_len);
+  out->restart_ht_len = snap.stats.restart_ht_len;
+  const int na = snap_group_na(gq.q.num_aggs);
+  const bool local = query->expect_groups <= (uint64_t)snap_group_local_slots(na);
+  out->local_level = local ? 1 : 0;
+  if (n == 0) return 0;
+
+  // the snapshot's global table, initialized as k_snap_group_init does
+  const uint64_t gcap = snap_group_table_cap(n);
+  std::vector<unsigned long long> gkey(gcap + 1, 0);
+  std::vector<unsigned> state(gcap + 1, 0);
+  std::vector<long long> gvals((gcap + 1) * YBG_MAX_AGGS, 0);
+  std::vector<unsigned long long> gcnts((gcap + 1) * YBG_MAX_AGGS, 0);
+  std::vector<unsigned long long> vals_hi((gcap + 1) * YBG_MAX_AGGS, 0);
+  std::vector<unsigned> poison((gcap + 1) * YBG_MAX_AGGS, 0);
+  SnapOps ops;
+  memset(&ops, 0, sizeof(ops));
+  ops.num_aggs = gq.q.num_aggs;
+  for (int g = 0; g < gq.q.num_aggs; ++g) ops.op[g] = gq.q.aggs[g].op;
+  for (uint64_t i = 0; i <= gcap; ++i)
+    for (int g = 0; g < ops.num_aggs; ++g)
+      gvals[i * YBG_MAX_AGGS + g] = group_init_value(ops.op[g]);
+  unsigned long long overflow = 0;
+  GroupCtx gc;
+  gc.gkey = gkey.data();
+  gc.state = state.data();
+  gc.vals = gvals.data();
+  gc.cnts = gcnts.data();
+  gc.vals_hi = vals_hi.data();
+  gc.poison = poison.data();
+  gc.cap = gcap;
+  gc.overflow = &overflow;
+  gc.data = nullptr;
+
+  uint64_t matched = 0;
+  switch (na) {
+    case 2: sim_group_dispatch<2>(gq, gc, local, &matched); break;
+    case 4: sim_group_dispatch<4>(gq, gc, local, &matched); break;
+    default: sim_group_dispatch<8>(gq, gc, local, &matched); break;
+  }
+  if (overflow) return 8;
+  out->rows_matched = matched;
+
+  // export: occupied slots ordered by key (unsigned), the NULL group last
+  std::vector<std::pair<uint64_t, uint64_t>> order;  // (key, slot)
+  for (uint64_t i = 0; i < gcap; ++i)
+    if (state[i] == 1) order.emplace_back(gkey[i], i);
+  std::sort(order.begin(), order.end());
+  const int has_null = state[gcap] == 1 ? 1 : 0;
+  out->n_groups = order.size() + (uint64_t)has_null;
+  out->has_null_group = has_null;
+  if (out->n_groups > cap) return 8;
+  for (uint64_t i = 0; i < order.size(); ++i)
+    snap_group_export_slot(ops, gc, order[i].second, order[i].first, i, keys,
+                           (long long*)vals, (unsigned long long*)cnts);
+  if (has_null)
+    snap_group_export_slot(ops, gc, gcap, 0, order.size(), keys,
+                           (long long*)vals, (unsigned long long*)cnts);
   return 0;
 }
 

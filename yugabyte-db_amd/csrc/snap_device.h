@@ -1,7 +1,8 @@
 // yugabyte-db_amd/csrc/snap_device.h — columnar-snapshot query logic: the
-// per-row predicate/aggregate evaluation over dense per-column arrays, and
-// the host-side translation of an ABI query into the POD kernel argument.
-// Compiled into the HIP query kernel (snap_gpu.hip) AND the host simulator
+// per-row predicate/aggregate evaluation over dense per-column arrays, the
+// grouped query's accumulate / flush / export, and the host-side
+// translation of an ABI query into the POD kernel argument.
+// Compiled into the HIP query kernels (snap_gpu.hip) AND the host simulator
 // (scan_host_sim.cc), with the same DEV macro convention as scan_device.h.
 //
 // A snapshot is a DIFFERENT storage contract from "scan the reference's
@@ -117,6 +118,342 @@ DEV void snap_row(const SnapQuery& q, const uint64_t* pv, const uint64_t* av,
     bool contrib = pass;
     if (NULLS) contrib = contrib & ((nm & a.null_m) == 0);
     if (contrib) combine_datum(a.op, &agg_val[g], &agg_cnt[g], av[g]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// GROUP BY on a snapshot. Every passing row is accumulated into a group
+// table with order-independent integer atomics (add / min / max / or; double
+// SUM as 128-bit 2^-60 fixed point), so the exported groups are bit-identical
+// whatever the arrival order and whichever of the two levels ran:
+//   LOCAL: a workgroup-local open-addressing table (LDS on the device, a
+//     heap array in the simulator) absorbs the rows; a row whose group finds
+//     no slot within kSnapLocalProbes probes goes straight to the global
+//     table; after the row loop the workgroup flushes every occupied local
+//     slot with ONE find-or-insert plus one set of atomics.
+//   global-only: every row goes to the global table (group_accum_from).
+// ---------------------------------------------------------------------------
+
+// Workgroup-scope accesses of the local table's claim protocol (agent scope
+// would write the L2 back on every release).
+#ifdef YBG_HOST_SIM
+static inline unsigned ybg_wg_load_u32(unsigned* p) { return *p; }
+static inline unsigned long long ybg_wg_load_u64(unsigned long long* p) {
+  return *p;
+}
+static inline void ybg_wg_store_u64(unsigned long long* p,
+                                    unsigned long long v) {
+  *p = v;
+}
+static inline void ybg_wg_store_rel_u32(unsigned* p, unsigned v) { *p = v; }
+#else
+__device__ __forceinline__ unsigned ybg_wg_load_u32(unsigned* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ unsigned long long ybg_wg_load_u64(
+    unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void ybg_wg_store_u64(unsigned long long* p,
+                                                 unsigned long long v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void ybg_wg_store_rel_u32(unsigned* p,
+                                                     unsigned v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+#endif
+
+// Aggregate cap (2 / 4 / 8) of the kernel instantiation a query selects.
+YBG_HD int snap_group_na(int32_t num_aggs) {
+  return num_aggs <= 2 ? 2 : (num_aggs <= 4 ? 4 : 8);
+}
+// Local-table slot count per aggregate cap: the widest power of two that
+// keeps the table (SnapLocalTable<NA>, 16 + 24 * NA bytes per slot) under
+// the 40 KiB that leave 4 workgroups per CU resident (kSnapMaxGrid).
+constexpr int snap_group_local_slots(int na_cap) {
+  return na_cap <= 2 ? 512 : (na_cap <= 4 ? 256 : 128);
+}
+// probes a row spends on the local table before it spills to the global one
+constexpr int kSnapLocalProbes = 4;
+// iterations of one local lookup, waits on a slot being claimed included
+constexpr int kSnapLocalIters = 64;
+
+// Global group-table capacity: smallest power of two >= 2 * n_rows, clamped
+// to [1024, 2^20].
+YBG_HD uint64_t snap_group_table_cap(uint64_t n_rows) {
+  uint64_t cap = 1024;
+  while (cap < 2 * n_rows && cap < (1ull << 20)) cap <<= 1;
+  return cap;
+}
+
+// Workgroup-local group table. Slot L is the NULL-key group. state[]:
+// 0 empty / 2 claiming / 1 ready, as in GroupCtx. poison[]: bit g = the
+// slot's double SUM of aggregate g met a value outside the fixed-point range.
+template <int NA>
+struct SnapLocalTable {
+  static constexpr int L = snap_group_local_slots(NA);
+  unsigned long long key[L + 1];
+  unsigned long long val[(L + 1) * NA];  // low word of a double SUM
+  unsigned long long hi[(L + 1) * NA];   // its high word
+  unsigned long long cnt[(L + 1) * NA];
+  unsigned state[L + 1];
+  unsigned poison[L + 1];
+};
+
+// The grouped query kernel's argument (POD, passed by value).
+struct SnapGroupQuery {
+  SnapQuery q;
+  const uint64_t* grp_col;  // staged group column
+  uint32_t grp_null_m;      // its null-mask bit (0: never NULL)
+  uint32_t pad_;
+};
+
+// One passing row, with group_accum_from's field names.
+struct SnapGroupRow {
+  uint64_t grp_datum;
+  uint64_t agg_datum[YBG_MAX_AGGS];
+  uint32_t grp_len;   // 0: numeric group key
+  uint32_t agg_null;  // bit g: operand of aggregate g is NULL
+  uint32_t grp_null;
+};
+
+struct SnapOps {
+  int32_t num_aggs;
+  int32_t op[YBG_MAX_AGGS];
+};
+
+// Slots [first, L] in steps of `step` back to empty (device: first =
+// threadIdx.x, step = blockDim.x, followed by a barrier).
+template <int NA>
+DEV void snap_local_init(const SnapQuery& q, SnapLocalTable<NA>* t,
+                         int first, int step) {
+  for (int i = first; i <= SnapLocalTable<NA>::L; i += step) {
+    t->key[i] = 0;
+    t->state[i] = 0;
+    t->poison[i] = 0;
+#pragma unroll
+    for (int g = 0; g < NA; ++g) {
+      t->val[i * NA + g] = (unsigned long long)group_init_value(
+          g < q.num_aggs ? q.aggs[g].op : 0);
+      t->hi[i * NA + g] = 0;
+      t->cnt[i * NA + g] = 0;
+    }
+  }
+}
+
+// Local slot of a non-NULL group key, or -1: no slot within
+// kSnapLocalProbes probes (the row then goes to the global table). As in
+// grp_find_or_insert, an iteration completes before a slot that is being
+// claimed is looked at again, so divergent lanes reconverge; the loop is
+// bounded either way.
+template <int NA>
+DEV int snap_local_find_or_insert(SnapLocalTable<NA>* t, uint64_t kv) {
+  constexpr unsigned mask = SnapLocalTable<NA>::L - 1;
+  const unsigned h = (unsigned)grp_mix(kv);
+  int probe = 0;
+  for (int it = 0; probe < kSnapLocalProbes && it < kSnapLocalIters; ++it) {
+    const unsigned i = (h + (unsigned)probe) & mask;
+    unsigned st = ybg_wg_load_u32(&t->state[i]);
+    if (st == 0) {
+      st = atomicCAS(&t->state[i], 0u, 2u);
+      if (st == 0) {
+        ybg_wg_store_u64(&t->key[i], kv);
+        ybg_wg_store_rel_u32(&t->state[i], 1u);
+        return (int)i;
+      }
+    }
+    if (st == 1) {
+      if (ybg_wg_load_u64(&t->key[i]) == kv) return (int)i;
+      ++probe;
+    }
+    // st == 2: another lane is publishing this slot; retry the same probe
+  }
+  return -1;
+}
+
+// Accumulate one passing row: local table first, global table on a miss.
+template <int NA>
+DEV void snap_local_accum(const SnapQuery& q, SnapLocalTable<NA>* t,
+                          const GroupCtx& gc, const SnapGroupRow& r) {
+  int slot;
+  if (r.grp_null) {
+    slot = SnapLocalTable<NA>::L;
+    if (ybg_wg_load_u32(&t->state[slot]) != 1)
+      ybg_wg_store_rel_u32(&t->state[slot], 1u);
+  } else {
+    slot = snap_local_find_or_insert<NA>(t, r.grp_datum);
+    if (slot < 0) {
+      group_accum_from<NA>(q, gc, r);
+      return;
+    }
+  }
+  unsigned long long* v = t->val + slot * NA;
+  unsigned long long* c = t->cnt + slot * NA;
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    if (g >= q.num_aggs) continue;
+    const int op = q.aggs[g].op;
+    if (op != YBG_AGG_COUNT_STAR && ((r.agg_null >> g) & 1)) continue;
+    const uint64_t d = r.agg_datum[g];
+    switch (op) {
+      case YBG_AGG_COUNT_STAR:
+      case YBG_AGG_COUNT:
+        atomicAdd(&v[g], 1ull);
+        break;
+      case YBG_AGG_SUM_INT64:
+        atomicAdd(&v[g], d);
+        break;
+      case YBG_AGG_SUM_DOUBLE: {
+        unsigned long long lo, hi;
+        if (f64_to_fixed128(d, &lo, &hi))
+          add_fixed128(&v[g], &t->hi[slot * NA + g], lo, hi);
+        else
+          ybg_atomic_or_u32(&t->poison[slot], 1u << g);
+        break;
+      }
+      case YBG_AGG_MIN_INT64:
+        ybg_atomic_min_i64((long long*)&v[g], (long long)d);
+        break;
+      case YBG_AGG_MAX_INT64:
+        ybg_atomic_max_i64((long long*)&v[g], (long long)d);
+        break;
+      case YBG_AGG_MIN_DOUBLE:
+        ybg_atomic_min_u64(&v[g], f64_ordered(d));
+        break;
+      case YBG_AGG_MAX_DOUBLE:
+        ybg_atomic_max_u64(&v[g], f64_ordered(d));
+        break;
+      default:
+        break;
+    }
+    // COUNT ops: cnt = val at export, as in the global table
+    if (op != YBG_AGG_COUNT_STAR && op != YBG_AGG_COUNT)
+      atomicAdd(&c[g], 1ull);
+  }
+}
+
+// Fold local slot i (0..L) into the global table: one find-or-insert, then
+// one atomic per aggregate word that holds a contribution. Runs after the
+// workgroup's rows are all in (device: behind a barrier).
+template <int NA>
+DEV void snap_local_flush_slot(const SnapQuery& q, SnapLocalTable<NA>* t,
+                               int i, const GroupCtx& gc) {
+  if (t->state[i] != 1) return;
+  uint64_t slot;
+  if (i == SnapLocalTable<NA>::L) {
+    slot = gc.cap;  // the NULL-key group
+    if (ybg_atomic_load_u32(&gc.state[slot]) != 1)
+      ybg_atomic_store_rel_u32(&gc.state[slot], 1u);
+  } else {
+    slot = grp_find_or_insert(gc, t->key[i], false);
+    if (slot == ~0ull) {
+      atomicAdd(gc.overflow, 1ull);
+      return;
+    }
+  }
+  long long* v = gc.vals + slot * YBG_MAX_AGGS;
+  unsigned long long* c = gc.cnts + slot * YBG_MAX_AGGS;
+  const unsigned poison = t->poison[i];
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    if (g >= q.num_aggs) continue;
+    const int op = q.aggs[g].op;
+    const unsigned long long lv = t->val[i * NA + g];
+    const unsigned long long lc = t->cnt[i * NA + g];
+    switch (op) {
+      case YBG_AGG_COUNT_STAR:
+      case YBG_AGG_COUNT:
+        if (lv) atomicAdd((unsigned long long*)&v[g], lv);
+        break;
+      case YBG_AGG_SUM_INT64:
+        if (lc) atomicAdd((unsigned long long*)&v[g], lv);
+        break;
+      case YBG_AGG_SUM_DOUBLE:
+        if ((poison >> g) & 1)
+          ybg_atomic_or_u32(&gc.poison[slot * YBG_MAX_AGGS + g], 1u);
+        if (lv | t->hi[i * NA + g])
+          group_add_fixed128(gc, slot, g, lv, t->hi[i * NA + g]);
+        break;
+      case YBG_AGG_MIN_INT64:
+        if (lc) ybg_atomic_min_i64(&v[g], (long long)lv);
+        break;
+      case YBG_AGG_MAX_INT64:
+        if (lc) ybg_atomic_max_i64(&v[g], (long long)lv);
+        break;
+      case YBG_AGG_MIN_DOUBLE:
+        if (lc) ybg_atomic_min_u64((unsigned long long*)&v[g], lv);
+        break;
+      case YBG_AGG_MAX_DOUBLE:
+        if (lc) ybg_atomic_max_u64((unsigned long long*)&v[g], lv);
+        break;
+      default:
+        break;
+    }
+    if (lc) atomicAdd(&c[g], lc);
+  }
+}
+
+// One row of the grouped query: snap_row's predicate fold, then the row's
+// group datum / aggregate operands into `tab` (LOCAL) or the global table.
+// gv: the row's group-column datum.
+template <int NP, int NA, bool NULLS, bool GEN, bool LOCAL>
+DEV void snap_group_row(const SnapGroupQuery& gq, const uint64_t* pv,
+                        const uint64_t* av, uint64_t gv, uint32_t nm,
+                        bool valid, uint64_t* matched,
+                        SnapLocalTable<NA>* tab, const GroupCtx& gc) {
+  const SnapQuery& q = gq.q;
+  bool pass = valid;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    if (i >= q.num_preds) continue;
+    const SnapPred& p = q.preds[i];
+    bool ok = GEN ? pred_compare(p.pc, pv[i], nullptr, 0, q.aux)
+                  : pred_cmp_fast(p.pc, pv[i]);
+    if (NULLS) ok = ok & ((nm & p.null_m) == 0);
+    pass = pass & ok;
+  }
+  if (!pass) return;
+  *matched += 1;
+  SnapGroupRow r;
+  r.grp_datum = gv;
+  r.grp_len = 0;
+  r.grp_null = NULLS ? ((nm & gq.grp_null_m) != 0) : 0;
+  r.agg_null = 0;
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    r.agg_datum[g] = av[g];
+    if (NULLS && g < q.num_aggs && (nm & q.aggs[g].null_m))
+      r.agg_null |= 1u << g;
+  }
+  if (LOCAL)
+    snap_local_accum<NA>(q, tab, gc, r);
+  else
+    group_accum_from<NA>(q, gc, r);
+}
+
+// Export of global-table slot `slot` as output entry `idx`: decoded values
+// and the COUNT cnt = val rule, all YBG_MAX_AGGS columns written (zero past
+// num_aggs) so the output bytes are a pure function of the groups.
+DEV void snap_group_export_slot(const SnapOps& ops, const GroupCtx& gc,
+                                uint64_t slot, uint64_t key, uint64_t idx,
+                                uint64_t* keys, long long* vals,
+                                unsigned long long* cnts) {
+  keys[idx] = key;
+  for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+    long long v = 0;
+    unsigned long long c = 0;
+    if (g < ops.num_aggs) {
+      const int op = ops.op[g];
+      v = group_export_value(op, gc.vals[slot * YBG_MAX_AGGS + g],
+                             gc.vals_hi[slot * YBG_MAX_AGGS + g],
+                             gc.poison[slot * YBG_MAX_AGGS + g]);
+      c = (op == YBG_AGG_COUNT_STAR || op == YBG_AGG_COUNT)
+              ? (unsigned long long)v
+              : gc.cnts[slot * YBG_MAX_AGGS + g];
+    }
+    vals[idx * YBG_MAX_AGGS + g] = v;
+    cnts[idx * YBG_MAX_AGGS + g] = c;
   }
 }
 
@@ -247,6 +584,61 @@ inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
   }
   // windowed-load tail slack for the option lists (load_u64_una)
   aux->insert(aux->end(), 16, 0);
+  return 0;
+}
+
+// ABI grouped query -> SnapGroupQuery: snap_build_query's rules for the
+// predicates and aggregates, plus the group column (any staged value or key
+// column) and at least one aggregate.
+inline int snap_build_group_query(const ybg_schema_t& sc,
+                                  const SnapCols* cols,
+                                  const ybg_snapshot_group_query_t& gq,
+                                  uint64_t n_rows, std::vector<uint8_t>* aux,
+                                  SnapGroupQuery* out, char* err,
+                                  size_t err_cap) {
+  memset(out, 0, sizeof(*out));
+  int rc = snap_build_query(sc, cols, gq.num_preds, gq.preds, gq.num_aggs,
+                            gq.aggs, n_rows, aux, &out->q, err, err_cap);
+  if (rc) return rc;
+  if (gq.num_aggs == 0) {
+    snprintf(err, err_cap,
+             "snapshot group query: num_aggs 0: a grouped query needs at "
+             "least one aggregate");
+    return 9;
+  }
+  const int nk = sc.num_hash_cols + sc.num_range_cols;
+  if (gq.group_is_key_col) {
+    if (gq.group_col < 0 || gq.group_col >= nk) {
+      snprintf(err, err_cap,
+               "snapshot group query: group column: key column %d out of "
+               "range", gq.group_col);
+      return 9;
+    }
+    if (sc.key_types[gq.group_col] == YBG_KT_STRING) {
+      snprintf(err, err_cap,
+               "snapshot group query: group column: string key column %d is "
+               "not staged", gq.group_col);
+      return 9;
+    }
+    if (cols) out->grp_col = cols->key[gq.group_col];
+  } else {
+    if (gq.group_col < 0 || gq.group_col >= sc.num_value_cols) {
+      snprintf(err, err_cap,
+               "snapshot group query: group column: value column %d out of "
+               "range", gq.group_col);
+      return 9;
+    }
+    if (sc.value_cols[gq.group_col].dtype == YBG_T_STRING) {
+      snprintf(err, err_cap,
+               "snapshot group query: group column: string column %d is not "
+               "staged", gq.group_col);
+      return 9;
+    }
+    if (cols) out->grp_col = cols->val[gq.group_col];
+    out->grp_null_m = 1u << gq.group_col;
+    const uint32_t nullable = cols ? cols->nullable_cols : 0xffffffffu;
+    if (nullable & out->grp_null_m) out->q.any_nullable = 1;
+  }
   return 0;
 }
 

@@ -15,6 +15,11 @@
 //    branch-free into a pass bit; lanes fold rows in ascending order, waves
 //    fold lanes in fixed order.
 //  * k_snap_reduce: one workgroup folds the wave partials in fixed order.
+//  * k_snap_group_query: GROUP BY on one staged column, same loads and
+//    launch; rows accumulate with order-independent integer atomics in a
+//    workgroup-local LDS table flushed into the snapshot's global group
+//    table (or straight into it); k_snap_group_init / _compact / _export
+//    reset the table and deliver the groups ordered by key.
 //  The grid is a pure function of n_rows, so together with the sorted
 //  build, results (double SUM included) are bit-identical across queries
 //  and across separately built snapshots of the same tablet.
@@ -127,11 +132,6 @@ __global__ __launch_bounds__(kSnapThreads) void k_snap_query(
   if (lane == 0) out[0] = matched;
 }
 
-struct SnapOps {
-  int32_t num_aggs;
-  int32_t op[YBG_MAX_AGGS];
-};
-
 // One workgroup: thread t folds partials t, t+256, ... in ascending order,
 // thread 0 folds the 256 thread results in order.
 __global__ __launch_bounds__(256) void k_snap_reduce(
@@ -173,6 +173,148 @@ __global__ __launch_bounds__(256) void k_snap_reduce(
     }
     __syncthreads();
   }
+}
+
+// ---------------------------------------------------------------------------
+// Grouped query. Same row-pair layout and launch as k_snap_query, with the
+// group column as one more 16-byte load. LOCAL: passing rows go to the
+// workgroup's LDS table (snap_local_accum), flushed into the global table
+// after the row loop; otherwise straight to the global table. Both barriers
+// sit outside the grid-stride loop. rows_matched: one integer add per wave.
+// ---------------------------------------------------------------------------
+template <int NP, int NA, bool NULLS, bool GEN, bool LOCAL>
+__global__ __launch_bounds__(kSnapThreads) void k_snap_group_query(
+    SnapGroupQuery gq, GroupCtx gc, unsigned long long* __restrict__ matched_out) {
+  const SnapQuery& q = gq.q;
+  const uint64_t n_pairs = (q.n_rows + kSnapVec - 1) / kSnapVec;
+  const uint64_t span = (uint64_t)gridDim.x * kSnapThreads;
+  SnapLocalTable<NA>* tab = nullptr;
+  if constexpr (LOCAL) {
+    __shared__ SnapLocalTable<NA> lds_tab;
+    static_assert(sizeof(SnapLocalTable<NA>) <= 40 * 1024,
+                  "4 workgroups per CU must stay resident");
+    tab = &lds_tab;
+    snap_local_init<NA>(q, tab, (int)threadIdx.x, kSnapThreads);
+    __syncthreads();
+  }
+  uint64_t matched = 0;
+
+  for (uint64_t pi = (uint64_t)blockIdx.x * kSnapThreads + threadIdx.x;
+       pi < n_pairs; pi += span) {
+    const uint64_t r0 = pi * kSnapVec;
+    // all column loads of the iteration back to back, before any compare
+    snap_u64x2 pv[NP], av[NA];
+    snap_u32x2 nm = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      pv[i] = snap_u64x2{0ull, 0ull};
+      if (i < q.num_preds)
+        pv[i] = *reinterpret_cast<const snap_u64x2*>(q.preds[i].col + r0);
+    }
+#pragma unroll
+    for (int g = 0; g < NA; ++g) {
+      av[g] = snap_u64x2{0ull, 0ull};
+      if (g < q.num_aggs && q.aggs[g].col)
+        av[g] = *reinterpret_cast<const snap_u64x2*>(q.aggs[g].col + r0);
+    }
+    const snap_u64x2 gv = *reinterpret_cast<const snap_u64x2*>(gq.grp_col + r0);
+    if (NULLS) nm = *reinterpret_cast<const snap_u32x2*>(q.nullmask + r0);
+
+    uint64_t p0[NP], p1[NP], a0[NA], a1[NA];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { p0[i] = pv[i].x; p1[i] = pv[i].y; }
+#pragma unroll
+    for (int g = 0; g < NA; ++g) { a0[g] = av[g].x; a1[g] = av[g].y; }
+    // the odd tail's padding row is masked
+    snap_group_row<NP, NA, NULLS, GEN, LOCAL>(gq, p0, a0, gv.x, nm.x, true,
+                                              &matched, tab, gc);
+    snap_group_row<NP, NA, NULLS, GEN, LOCAL>(gq, p1, a1, gv.y, nm.y,
+                                              r0 + 1 < q.n_rows, &matched,
+                                              tab, gc);
+  }
+
+  if constexpr (LOCAL) {
+    __syncthreads();
+    for (int i = (int)threadIdx.x; i <= SnapLocalTable<NA>::L;
+         i += kSnapThreads)
+      snap_local_flush_slot<NA>(q, tab, i, gc);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    matched += __shfl_down((unsigned long long)matched, off);
+  if ((threadIdx.x & 63) == 0 && matched)
+    atomicAdd(matched_out, (unsigned long long)matched);
+}
+
+// Per-query reset of the global group table (slot cap = the NULL group).
+__global__ __launch_bounds__(256) void k_snap_group_init(SnapOps ops,
+                                                         GroupCtx gc) {
+  uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (; i <= gc.cap; i += stride) {
+    gc.state[i] = 0;
+    gc.gkey[i] = 0;
+    for (int g = 0; g < ops.num_aggs; ++g) {
+      gc.vals[i * YBG_MAX_AGGS + g] = group_init_value(ops.op[g]);
+      gc.cnts[i * YBG_MAX_AGGS + g] = 0;
+      gc.vals_hi[i * YBG_MAX_AGGS + g] = 0;
+      gc.poison[i * YBG_MAX_AGGS + g] = 0;
+    }
+  }
+}
+
+constexpr int kCompactThreads = 1024;
+
+// Occupied non-NULL slots -> (key, slot) pairs in arrival order (the sort
+// that follows makes the order canonical): one atomic per workgroup.
+// counters[0] = pairs written.
+__global__ __launch_bounds__(kCompactThreads) void k_snap_group_compact(
+    GroupCtx gc, uint64_t* __restrict__ ckeys, uint32_t* __restrict__ cslots,
+    unsigned long long* __restrict__ counters) {
+  __shared__ unsigned wave_cnt[kCompactThreads / 64];
+  __shared__ unsigned long long wg_base;
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t n_tiles = (gc.cap + kCompactThreads - 1) / kCompactThreads;
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t i = tile * kCompactThreads + threadIdx.x;
+    const bool occ = i < gc.cap && gc.state[i] == 1;
+    const unsigned long long m = __ballot(occ);
+    if (lane == 0) wave_cnt[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned total = 0;
+      for (int w = 0; w < kCompactThreads / 64; ++w) {
+        const unsigned c = wave_cnt[w];
+        wave_cnt[w] = total;
+        total += c;
+      }
+      wg_base = total ? atomicAdd(&counters[0], (unsigned long long)total) : 0;
+    }
+    __syncthreads();
+    if (occ) {
+      const uint64_t at = wg_base + wave_cnt[wave] +
+                          (unsigned)__popcll(m & ((1ull << lane) - 1));
+      ckeys[at] = gc.gkey[i];
+      cslots[at] = (uint32_t)i;
+    }
+    __syncthreads();
+  }
+}
+
+// Entry i < n_sorted: the group in slot sslots[i] (keys ascending). Entry
+// n_sorted, when has_null: the NULL group (slot cap), key 0.
+__global__ __launch_bounds__(256) void k_snap_group_export(
+    SnapOps ops, GroupCtx gc, const uint64_t* __restrict__ skeys,
+    const uint32_t* __restrict__ sslots, uint64_t n_sorted, int has_null,
+    uint64_t* __restrict__ out_keys, long long* __restrict__ out_vals,
+    unsigned long long* __restrict__ out_cnts) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_sorted)
+    snap_group_export_slot(ops, gc, sslots[i], skeys[i], i, out_keys,
+                           out_vals, out_cnts);
+  else if (i == n_sorted && has_null)
+    snap_group_export_slot(ops, gc, gc.cap, 0, i, out_keys, out_vals,
+                           out_cnts);
 }
 
 // ---------------------------------------------------------------------------
@@ -261,6 +403,18 @@ struct ybg_snapshot {
   bool pending = false;            // a launched query awaits its fetch
   bool timed = false;              // that query recorded events
   SnapResult h_result;
+  // grouped queries: the global group table and the export scratch, all
+  // allocated by the first grouped query (device_bytes counts them)
+  GroupCtx grp = {};               // cap = snap_group_table_cap(n_rows)
+  unsigned long long* d_gctr = nullptr;  // {pairs, overflow, matched}
+  uint64_t* d_gkeys = nullptr;     // [2 * cap] compacted / sorted keys
+  uint32_t* d_gslots = nullptr;    // [2 * cap] their table slots
+  void* d_gsort = nullptr;         // radix sort temporary storage
+  size_t gsort_bytes = 0;
+  uint64_t* d_gout_keys = nullptr;  // [gout_cap] export, grown on demand
+  long long* d_gout_vals = nullptr;
+  unsigned long long* d_gout_cnts = nullptr;
+  uint64_t gout_cap = 0;
 };
 
 namespace {
@@ -274,10 +428,43 @@ void snap_free(ybg_snapshot* sn) {
   if (sn->d_partials) HIP_WARN(hipFree(sn->d_partials));
   if (sn->d_result) HIP_WARN(hipFree(sn->d_result));
   if (sn->d_aux) HIP_WARN(hipFree(sn->d_aux));
+  void* grouped[] = {sn->grp.gkey, sn->grp.state, sn->grp.vals, sn->grp.cnts,
+                     sn->grp.vals_hi, sn->grp.poison, sn->d_gctr, sn->d_gkeys,
+                     sn->d_gslots, sn->d_gsort, sn->d_gout_keys,
+                     sn->d_gout_vals, sn->d_gout_cnts};
+  for (void* p : grouped)
+    if (p) HIP_WARN(hipFree(p));
   if (sn->ev_q0) HIP_WARN(hipEventDestroy(sn->ev_q0));
   if (sn->ev_q1) HIP_WARN(hipEventDestroy(sn->ev_q1));
   if (sn->stream) HIP_WARN(hipStreamDestroy(sn->stream));
   delete sn;
+}
+
+SnapCols snap_cols(const ybg_snapshot* sn) {
+  SnapCols cols;
+  memset(&cols, 0, sizeof(cols));
+  for (int c = 0; c < YBG_MAX_COLS; ++c) cols.val[c] = sn->d_val[c];
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c) cols.key[c] = sn->d_key[c];
+  cols.nullmask = sn->d_nullmask;
+  cols.nullable_cols = sn->nullable_cols;
+  return cols;
+}
+
+// IN / IN_RANGE lists of q (sn->aux_host) to the device, async on the
+// snapshot's stream; sets q->aux.
+int snap_upload_aux(ybg_snapshot* sn, SnapQuery* q) {
+  if (!q->general) return 0;
+  if (sn->aux_host.size() > sn->aux_cap) {
+    if (sn->d_aux) HIP_WARN(hipFree(sn->d_aux));
+    sn->d_aux = nullptr;
+    sn->aux_cap = 0;
+    HIP_TRY(hipMalloc(&sn->d_aux, sn->aux_host.size()));
+    sn->aux_cap = sn->aux_host.size();
+  }
+  HIP_TRY(hipMemcpyAsync(sn->d_aux, sn->aux_host.data(), sn->aux_host.size(),
+                         hipMemcpyHostToDevice, sn->stream));
+  q->aux = sn->d_aux;
+  return 0;
 }
 
 template <int NP, int NA>
@@ -295,12 +482,7 @@ void snap_launch_fast(const SnapQuery& q, int grid, hipStream_t st,
 // nothing and leaves the snapshot usable.
 int snap_launch(ybg_snapshot* sn, int32_t num_preds, const ybg_pred_t* preds,
                 int32_t num_aggs, const ybg_agg_t* aggs) {
-  SnapCols cols;
-  memset(&cols, 0, sizeof(cols));
-  for (int c = 0; c < YBG_MAX_COLS; ++c) cols.val[c] = sn->d_val[c];
-  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c) cols.key[c] = sn->d_key[c];
-  cols.nullmask = sn->d_nullmask;
-  cols.nullable_cols = sn->nullable_cols;
+  const SnapCols cols = snap_cols(sn);
   SnapQuery q;
   char err[192];
   // the previous query's lists may still be in flight from aux_host
@@ -319,19 +501,7 @@ int snap_launch(ybg_snapshot* sn, int32_t num_preds, const ybg_pred_t* preds,
     sn->pending = true;
     return 0;
   }
-  if (q.general) {
-    if (sn->aux_host.size() > sn->aux_cap) {
-      if (sn->d_aux) HIP_WARN(hipFree(sn->d_aux));
-      sn->d_aux = nullptr;
-      sn->aux_cap = 0;
-      HIP_TRY(hipMalloc(&sn->d_aux, sn->aux_host.size()));
-      sn->aux_cap = sn->aux_host.size();
-    }
-    HIP_TRY(hipMemcpyAsync(sn->d_aux, sn->aux_host.data(),
-                           sn->aux_host.size(), hipMemcpyHostToDevice,
-                           sn->stream));
-    q.aux = sn->d_aux;
-  }
+  if (int arc = snap_upload_aux(sn, &q)) return arc;
   const int grid = (int)snap_grid(sn->n_rows);
   HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
   if (q.general) {
@@ -390,6 +560,206 @@ int snap_finish(ybg_snapshot* sn, int32_t num_aggs, const ybg_agg_t* aggs,
   if (out)
     snap_fill_result(sn->h_result, sn->n_rows, sn->entries_seen,
                      sn->restart_ht, sn->restart_len, num_aggs, aggs, out);
+  return 0;
+}
+
+// ---- grouped query ---------------------------------------------------------
+
+struct GroupLaunch {
+  const SnapGroupQuery* gq;
+  const GroupCtx* gc;
+  unsigned long long* matched;
+  int grid;
+  hipStream_t st;
+  bool local;
+};
+
+template <int NP, int NA, bool GEN>
+void snap_group_launch_na(const GroupLaunch& l) {
+  const dim3 g(l.grid), b(kSnapThreads);
+  const bool nulls = l.gq->q.any_nullable;
+  if (l.local) {
+    if (nulls)
+      hipLaunchKernelGGL((k_snap_group_query<NP, NA, true, GEN, true>), g, b,
+                         0, l.st, *l.gq, *l.gc, l.matched);
+    else
+      hipLaunchKernelGGL((k_snap_group_query<NP, NA, false, GEN, true>), g, b,
+                         0, l.st, *l.gq, *l.gc, l.matched);
+  } else {
+    if (nulls)
+      hipLaunchKernelGGL((k_snap_group_query<NP, NA, true, GEN, false>), g, b,
+                         0, l.st, *l.gq, *l.gc, l.matched);
+    else
+      hipLaunchKernelGGL((k_snap_group_query<NP, NA, false, GEN, false>), g,
+                         b, 0, l.st, *l.gq, *l.gc, l.matched);
+  }
+}
+
+// NA follows num_aggs for the IN / IN_RANGE kernels too, so the local slot
+// count is a function of num_aggs alone (ybg_snapshot_group_local_slots).
+template <int NP, bool GEN>
+void snap_group_launch_np(const GroupLaunch& l) {
+  switch (snap_group_na(l.gq->q.num_aggs)) {
+    case 2: snap_group_launch_na<NP, 2, GEN>(l); break;
+    case 4: snap_group_launch_na<NP, 4, GEN>(l); break;
+    default: snap_group_launch_na<NP, 8, GEN>(l); break;
+  }
+}
+
+template <class T>
+int snap_group_alloc(ybg_snapshot* sn, T** p, size_t bytes) {
+  if (*p) return 0;  // kept from an earlier, partly failed attempt
+  HIP_TRY(hipMalloc(p, bytes));
+  sn->device_bytes += bytes;
+  return 0;
+}
+
+// First grouped query: the global table and the compaction / sort scratch.
+int snap_group_ensure_table(ybg_snapshot* sn) {
+  if (sn->grp.cap) return 0;
+  const uint64_t cap = snap_group_table_cap(sn->n_rows);
+  const uint64_t n = cap + 1, na = n * YBG_MAX_AGGS;
+  GroupCtx& gc = sn->grp;
+  int rc = 0;
+  if ((rc = snap_group_alloc(sn, &gc.gkey, n * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &gc.state, n * 4))) return rc;
+  if ((rc = snap_group_alloc(sn, &gc.vals, na * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &gc.cnts, na * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &gc.vals_hi, na * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &gc.poison, na * 4))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_gctr, 3 * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_gkeys, 2 * cap * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_gslots, 2 * cap * 4))) return rc;
+  gc.overflow = sn->d_gctr + 1;
+  gc.data = nullptr;
+  gc.cap = cap;  // last: marks the table as allocated
+  return 0;
+}
+
+int snap_group_query(ybg_snapshot* sn, const ybg_snapshot_group_query_t* gqa,
+                     uint64_t* keys, int64_t* vals, uint64_t* cnts,
+                     uint64_t cap, ybg_snapshot_group_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  const SnapCols cols = snap_cols(sn);
+  SnapGroupQuery gq;
+  char err[192];
+  // a launched plain query may still read aux_host / d_aux
+  if (sn->pending) HIP_TRY(hipStreamSynchronize(sn->stream));
+  sn->aux_host.clear();
+  int rc = snap_build_group_query(sn->schema, &cols, *gqa, sn->n_rows,
+                                  &sn->aux_host, &gq, err, sizeof(err));
+  if (rc) return set_err(rc, err);
+  out->rows_scanned = sn->n_rows;
+  out->entries_seen = sn->entries_seen;
+  memcpy(out->restart_ht, sn->restart_ht, sn->restart_len);
+  out->restart_ht_len = sn->restart_len;
+  const int na = snap_group_na(gq.q.num_aggs);
+  const bool local = gqa->expect_groups <= (uint64_t)snap_group_local_slots(na);
+  out->local_level = local ? 1 : 0;
+  sn->last_query_ms = 0;
+  if (sn->n_rows == 0) return 0;  // no rows, no groups: nothing launched
+
+  if ((rc = snap_group_ensure_table(sn))) return rc;
+  if ((rc = snap_upload_aux(sn, &gq.q))) return rc;
+  const GroupCtx& gc = sn->grp;
+  SnapOps ops;
+  memset(&ops, 0, sizeof(ops));
+  ops.num_aggs = gq.q.num_aggs;
+  for (int g = 0; g < gq.q.num_aggs; ++g) ops.op[g] = gq.q.aggs[g].op;
+
+  HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+  HIP_TRY(hipMemsetAsync(sn->d_gctr, 0, 3 * 8, sn->stream));
+  const int init_grid = (int)((gc.cap + 1 + 255) / 256 < 2048
+                                  ? (gc.cap + 1 + 255) / 256 : 2048);
+  hipLaunchKernelGGL(k_snap_group_init, dim3(init_grid), dim3(256), 0,
+                     sn->stream, ops, gc);
+  GroupLaunch l{&gq, &gc, sn->d_gctr + 2, (int)snap_grid(sn->n_rows),
+                sn->stream, local};
+  if (gq.q.general) snap_group_launch_np<8, true>(l);
+  else if (gq.q.num_preds <= 4) snap_group_launch_np<4, false>(l);
+  else snap_group_launch_np<8, false>(l);
+  const int cgrid = (int)((gc.cap + kCompactThreads - 1) / kCompactThreads < 256
+                              ? (gc.cap + kCompactThreads - 1) / kCompactThreads
+                              : 256);
+  hipLaunchKernelGGL(k_snap_group_compact, dim3(cgrid), dim3(kCompactThreads),
+                     0, sn->stream, gc, sn->d_gkeys, sn->d_gslots, sn->d_gctr);
+  // the group count sizes the sort and the export
+  unsigned long long ctr[3] = {0, 0, 0};
+  unsigned null_state = 0;
+  HIP_TRY(hipMemcpyAsync(ctr, sn->d_gctr, sizeof(ctr), hipMemcpyDeviceToHost,
+                         sn->stream));
+  HIP_TRY(hipMemcpyAsync(&null_state, gc.state + gc.cap, 4,
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  if (ctr[1]) return set_err(8, "snapshot group query: group table overflow");
+  const uint64_t n_sorted = ctr[0];
+  const int has_null = null_state == 1 ? 1 : 0;
+  const uint64_t total = n_sorted + (uint64_t)has_null;
+  out->rows_matched = ctr[2];
+  out->n_groups = total;
+  out->has_null_group = has_null;
+  if (total > cap)
+    return set_err(8, "snapshot group query: " + std::to_string(total) +
+                          " groups exceed the output capacity " +
+                          std::to_string(cap));
+  if (total) {
+    if (total > sn->gout_cap) {
+      void* old[] = {sn->d_gout_keys, sn->d_gout_vals, sn->d_gout_cnts};
+      for (void* p : old)
+        if (p) HIP_WARN(hipFree(p));
+      sn->d_gout_keys = nullptr;
+      sn->d_gout_vals = nullptr;
+      sn->d_gout_cnts = nullptr;
+      sn->device_bytes -= sn->gout_cap * 8 * (1 + 2 * YBG_MAX_AGGS);
+      sn->gout_cap = 0;
+      uint64_t want = 1024;
+      while (want < total) want <<= 1;
+      if ((rc = snap_group_alloc(sn, &sn->d_gout_keys, want * 8))) return rc;
+      if ((rc = snap_group_alloc(sn, &sn->d_gout_vals,
+                                 want * 8 * YBG_MAX_AGGS)))
+        return rc;
+      if ((rc = snap_group_alloc(sn, &sn->d_gout_cnts,
+                                 want * 8 * YBG_MAX_AGGS)))
+        return rc;
+      sn->gout_cap = want;
+    }
+    uint64_t* skeys = sn->d_gkeys + gc.cap;
+    uint32_t* sslots = sn->d_gslots + gc.cap;
+    if (n_sorted) {
+      size_t need = 0;
+      HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, sn->d_gkeys, skeys,
+                                        sn->d_gslots, sslots,
+                                        (size_t)n_sorted, 0, 64, sn->stream));
+      if (need > sn->gsort_bytes) {
+        if (sn->d_gsort) HIP_WARN(hipFree(sn->d_gsort));
+        sn->d_gsort = nullptr;
+        sn->device_bytes -= sn->gsort_bytes;
+        sn->gsort_bytes = 0;
+        if ((rc = snap_group_alloc(sn, &sn->d_gsort, need))) return rc;
+        sn->gsort_bytes = need;
+      }
+      HIP_TRY(rocprim::radix_sort_pairs(sn->d_gsort, need, sn->d_gkeys, skeys,
+                                        sn->d_gslots, sslots,
+                                        (size_t)n_sorted, 0, 64, sn->stream));
+    }
+    hipLaunchKernelGGL(k_snap_group_export, dim3((int)((total + 255) / 256)),
+                       dim3(256), 0, sn->stream, ops, gc, skeys, sslots,
+                       n_sorted, has_null, sn->d_gout_keys, sn->d_gout_vals,
+                       sn->d_gout_cnts);
+  }
+  HIP_TRY(hipEventRecord(sn->ev_q1, sn->stream));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(keys, sn->d_gout_keys, total * 8,
+                           hipMemcpyDeviceToHost, sn->stream));
+    HIP_TRY(hipMemcpyAsync(vals, sn->d_gout_vals, total * 8 * YBG_MAX_AGGS,
+                           hipMemcpyDeviceToHost, sn->stream));
+    HIP_TRY(hipMemcpyAsync(cnts, sn->d_gout_cnts, total * 8 * YBG_MAX_AGGS,
+                           hipMemcpyDeviceToHost, sn->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, sn->ev_q0, sn->ev_q1));
+  sn->last_query_ms = ms;
   return 0;
 }
 
@@ -641,6 +1011,18 @@ int yb_gpu_snapshot_query(ybg_snapshot_t* sn, const ybg_snapshot_query_t* q,
   int rc = snap_launch(sn, q->num_preds, q->preds, q->num_aggs, q->aggs);
   if (rc) return rc;
   return snap_finish(sn, q->num_aggs, q->aggs, out);
+}
+
+int yb_gpu_snapshot_group_query(ybg_snapshot_t* sn,
+                                const ybg_snapshot_group_query_t* q,
+                                uint64_t* keys, int64_t* vals, uint64_t* cnts,
+                                uint64_t cap,
+                                ybg_snapshot_group_result_t* out) {
+  return snap_group_query(sn, q, keys, vals, cnts, cap, out);
+}
+
+uint64_t ybg_snapshot_group_local_slots(int32_t num_aggs) {
+  return (uint64_t)snap_group_local_slots(snap_group_na(num_aggs));
 }
 
 int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t* sn, double* query_ms) {

@@ -4,10 +4,15 @@
 // It walks the row-count edge table of tests/snapshot_cases.py — sizes
 // around the two-rows-per-lane, wave and workgroup tails, plus the empty
 // snapshot — and cross-checks every result against the block-path
-// simulator (ybg_sim_scan) on the same tablet and query. TEST
-// INFRASTRUCTURE; not linked into the product library.
+// simulator (ybg_sim_scan) on the same tablet and query. The grouped query
+// runs over the same table at both levels (workgroup-local table + flush,
+// global table only), grouped on the int32 value column, and is
+// cross-checked against the block-path GROUP BY simulator (ybg_sim_group).
+// TEST INFRASTRUCTURE; not linked into the product library.
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <vector>
 
 #include "../../include/yb_gpu_scan.h"
 
@@ -18,12 +23,80 @@ extern "C" int ybg_sim_snapshot_query(const ybg_scan_spec_t*, const uint8_t*,
                                       const ybg_snapshot_query_t*,
                                       ybg_scan_result_t*);
 
+extern "C" int ybg_sim_snapshot_group_query(
+    const ybg_scan_spec_t*, const uint8_t*, const uint64_t*, uint64_t,
+    const ybg_snapshot_group_query_t*, uint64_t*, int64_t*, uint64_t*,
+    uint64_t, ybg_snapshot_group_result_t*);
+extern "C" int ybg_sim_group(const ybg_scan_spec_t*, const uint8_t*,
+                             const uint64_t*, uint64_t, uint64_t*, long long*,
+                             unsigned long long*, uint8_t*, uint64_t,
+                             uint64_t, uint64_t*, uint8_t*, uint32_t*);
+
 namespace {
 
 uint64_t f64_bits(double d) {
   uint64_t u;
   memcpy(&u, &d, 8);
   return u;
+}
+
+// Grouped on value column 2 (int32, r % 1000: never NULL, never -1, so the
+// block path's ~0 NULL marker cannot collide). spec carries q's predicates
+// and aggregates (the block-path form); both levels must equal ybg_sim_group
+// entry for entry — double SUM included, both being exact fixed-point sums —
+// and come out in ascending key order.
+int check_grouped(ybg_scan_spec_t spec, const uint8_t* data,
+                  const uint64_t* offsets, uint64_t n_blocks,
+                  const ybg_snapshot_query_t& q) {
+  const uint64_t cap = 2048;
+  std::vector<uint64_t> bkeys(cap);
+  std::vector<long long> bvals(cap * YBG_MAX_AGGS);
+  std::vector<unsigned long long> bcnts(cap * YBG_MAX_AGGS);
+  uint64_t bn = 0;
+  spec.group_col = 2 + 1;
+  int bad = ybg_sim_group(&spec, data, offsets, n_blocks, bkeys.data(),
+                          bvals.data(), bcnts.data(), nullptr, 0, cap, &bn,
+                          nullptr, nullptr);
+  std::map<uint64_t, uint64_t> want;  // key -> block-path entry
+  for (uint64_t i = 0; i < bn; ++i) want[bkeys[i]] = i;
+
+  ybg_snapshot_group_query_t gq;
+  memset(&gq, 0, sizeof(gq));
+  gq.num_preds = q.num_preds;
+  memcpy(gq.preds, q.preds, sizeof(gq.preds));
+  gq.num_aggs = q.num_aggs;
+  memcpy(gq.aggs, q.aggs, sizeof(gq.aggs));
+  gq.group_col = 2;
+  ybg_scan_spec_t bs = spec;  // the snapshot build ignores all of these
+  bs.num_preds = 0;
+  bs.num_aggs = 0;
+  bs.group_col = 0;
+  // hint 1: two-level; 2^20: above every local slot count, global-only
+  for (uint64_t hint : {(uint64_t)1, (uint64_t)1 << 20}) {
+    std::vector<uint64_t> keys(cap), cnts(cap * YBG_MAX_AGGS);
+    std::vector<int64_t> vals(cap * YBG_MAX_AGGS);
+    ybg_snapshot_group_result_t res;
+    gq.expect_groups = hint;
+    int rc = ybg_sim_snapshot_group_query(&bs, data, offsets, n_blocks, &gq,
+                                          keys.data(), vals.data(),
+                                          cnts.data(), cap, &res);
+    int lbad = rc || res.n_groups != bn || res.has_null_group ||
+               res.local_level != (hint == 1 ? 1 : 0);
+    for (uint64_t i = 0; i < res.n_groups && !lbad; ++i) {
+      auto it = want.find(keys[i]);
+      lbad = it == want.end() || (i > 0 && keys[i - 1] >= keys[i]);
+      for (int g = 0; g < q.num_aggs && !lbad; ++g)
+        lbad = vals[i * YBG_MAX_AGGS + g] !=
+                   bvals[it->second * YBG_MAX_AGGS + g] ||
+               cnts[i * YBG_MAX_AGGS + g] !=
+                   bcnts[it->second * YBG_MAX_AGGS + g];
+    }
+    printf("  grouped hint=%llu: groups=%llu matched=%llu %s\n",
+           (unsigned long long)hint, (unsigned long long)res.n_groups,
+           (unsigned long long)res.rows_matched, lbad ? "MISMATCH" : "ok");
+    bad |= lbad;
+  }
+  return bad;
 }
 
 int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
@@ -78,6 +151,7 @@ int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
          (unsigned long long)n, (unsigned long long)read_micros, (int)nulls,
          (unsigned long long)snap.rows_scanned,
          (unsigned long long)snap.rows_matched, bad ? "MISMATCH" : "ok");
+  bad |= check_grouped(spec, data, offsets, n_blocks, q);
   ybg_builder_destroy(b);
   return bad;
 }
