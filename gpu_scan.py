@@ -70,6 +70,11 @@ def _lib():
         C.c_void_p, C.POINTER(y.SnapshotGroupQuery), C.POINTER(C.c_uint64),
         C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64,
         C.POINTER(y.SnapshotGroupResult)]
+    lib.yb_gpu_snapshot_select.restype = C.c_int
+    lib.yb_gpu_snapshot_select.argtypes = [
+        C.c_void_p, C.POINTER(y.SnapshotSelect), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64,
+        C.POINTER(y.SnapshotSelectResult)]
     lib.yb_gpu_snapshot_kernel_ms.restype = C.c_int
     lib.yb_gpu_snapshot_kernel_ms.argtypes = [C.c_void_p,
                                               C.POINTER(C.c_double)]
@@ -236,7 +241,7 @@ class GpuScan:
 class GpuSnapshot:
     """Columnar snapshot: the rows visible at one read time as dense
     device-resident column arrays, answering numeric predicate/aggregate
-    queries with the streaming query kernel."""
+    queries, GROUP BY and ordered row fetches with the streaming kernels."""
 
     def __init__(self, lib, handle):
         self._lib = lib
@@ -304,6 +309,50 @@ class GpuSnapshot:
         keys, vals, cnts, res = self.group_query_raw(
             preds, aggs, group_col, group_is_key, expect_groups, cap)
         return y.decode_snapshot_groups(res, keys, vals, cnts, list(aggs))
+
+    def select_raw(self, preds, cols, limit=0, backward=False, row_lo=0,
+                   row_hi=None, cap=1 << 16):
+        """Row fetch on the snapshot (yb_gpu_snapshot_select): raw ctypes
+        arrays (datums, null_masks, row_ids) plus the SnapshotSelectResult.
+        The first result.n_rows rows are written, ascending by snapshot
+        position (descending with backward); projected column j of row i is
+        datums[j * cap + i]. Output buffers are allocated once per
+        (capacity, column count) and reused, like group_query_raw's. Errors
+        raise GpuScanError with .code (9 unsupported query, 8 cap too small)
+        and .result."""
+        ncols = max(1, min(len(cols), y.MAX_SELECT_COLS))
+        sb = getattr(self, "_select_bufs", None)
+        if sb is None or sb[0] != (cap, ncols):
+            n = max(cap, 1)
+            sb = ((cap, ncols), (C.c_uint64 * (n * ncols))(),
+                  (C.c_uint32 * n)(), (C.c_uint64 * n)())
+            self._select_bufs = sb
+        datums, null_masks, row_ids = sb[1], sb[2], sb[3]
+        q = y.snapshot_select(preds, cols, limit, backward, row_lo, row_hi)
+        res = y.SnapshotSelectResult()
+        rc = self._lib.yb_gpu_snapshot_select(
+            self._h, C.byref(q), datums, null_masks, row_ids, cap,
+            C.byref(res))
+        if rc:
+            err = GpuScanError(
+                f"snapshot_select rc={rc}: "
+                f"{self._lib.yb_gpu_last_error().decode()}")
+            err.code = rc
+            err.result = res
+            raise err
+        return datums, null_masks, row_ids, res
+
+    def select(self, preds, cols, limit=0, backward=False, row_lo=0,
+               row_hi=None, cap=1 << 16):
+        """SELECT cols WHERE preds on the snapshot, in key order: returns
+        (rows, result) with rows = [(projected values..., None for NULL)].
+        cols: (is_key_col, col) pairs. Page with limit and
+        result.resume_row (the next row_lo, or row_hi when backward) until
+        result.done."""
+        datums, null_masks, _ids, res = self.select_raw(
+            preds, cols, limit, backward, row_lo, row_hi, cap)
+        return y.decode_snapshot_rows(res, datums, null_masks,
+                                      len(cols), cols, cap), res
 
     def kernel_ms(self):
         ms = C.c_double()

@@ -494,6 +494,78 @@ int yb_gpu_snapshot_group_query(ybg_snapshot_t *sn,
  * aggregates selects (tests derive cardinalities from it). */
 uint64_t ybg_snapshot_group_local_slots(int32_t num_aggs);
 
+/* SELECT on a snapshot: the matching rows themselves, in tablet key order,
+ * with a projection, a position window, a row limit and a resume position.
+ *
+ *   yb_gpu_snapshot_select ~ PgsqlReadOperation::ExecuteScalar row loop +
+ *                            PgFetchNext over the staged rows
+ *                            (pgsql_operation.cc:2808-2931); resume_row
+ *                            plays the role of SetPagingState's next row
+ *                            key (pgsql_operation.cc:2796-2806, 2908-2922)
+ */
+#define YBG_MAX_SELECT_COLS (YBG_MAX_COLS + YBG_MAX_KEYCOLS)
+typedef struct { int32_t is_key_col; int32_t col; } ybg_select_col_t;   /* as ybg_pred_t.is_key_col / .col */
+
+typedef struct {
+  int32_t num_preds; ybg_pred_t preds[YBG_MAX_PREDS];        /* rules of yb_gpu_snapshot_query */
+  int32_t num_cols;  ybg_select_col_t cols[YBG_MAX_SELECT_COLS]; /* projection, 1..cap, repeats allowed */
+  int32_t backward;          /* 1: deliver in descending key order */
+  uint64_t row_lo, row_hi;   /* window of snapshot positions [row_lo, row_hi); row_hi is clamped to n_rows
+                                (UINT64_MAX = to the end); row_lo >= row_hi is an empty window */
+  uint64_t row_limit;        /* 0 = unlimited */
+} ybg_snapshot_select_t;
+
+typedef struct {
+  uint64_t n_rows;           /* rows delivered */
+  uint64_t rows_scanned;     /* positions in the window */
+  uint64_t rows_matched;     /* matching rows in the window (>= n_rows) */
+  uint64_t resume_row;       /* see Paging */
+  int32_t  done;             /* 1: every matching row of the window was delivered */
+  uint64_t entries_seen; uint8_t restart_ht[YBG_MAX_HT]; uint32_t restart_ht_len;  /* the build's */
+} ybg_snapshot_select_result_t;
+
+/* Synchronous, on the snapshot's own stream, like the other two queries.
+ * row_ids / null_masks: [cap]; datums: [num_cols * cap].
+ * Order: a position is a row's index in the snapshot; snapshot rows are held
+ *   in tablet key order. Delivered rows are ascending by position, or
+ *   descending with backward.
+ * row_ids[i]: delivered row i's position.
+ * datums: column-major — projected column j of delivered row i is at
+ *   datums[j * cap + i], in the bit pattern yb_gpu_scan_next_batch delivers.
+ *   The datum of a NULL is written as 0.
+ * null_masks[i]: ybg_row_batch_t.null_masks layout (bit c = value column c
+ *   is NULL), masked to the projected value columns, so the output bytes are
+ *   a pure function of the rows. Key columns are never NULL.
+ * Limit: forward delivers the first row_limit matches of the window,
+ *   backward the last row_limit matches, highest first. rows_matched always
+ *   counts every match in the window.
+ * Paging: done = (n_rows == rows_matched). Forward: resume_row is the last
+ *   delivered position + 1, or row_hi (clamped) when done; the next page
+ *   passes it as row_lo. Backward: resume_row is the last (lowest) delivered
+ *   position, or row_lo when done; the next page passes it as row_hi. The
+ *   concatenated pages equal the unlimited result exactly.
+ * Determinism: datums, null_masks and row_ids are byte-identical across
+ *   repeated calls and across separately built snapshots of the same tablet.
+ * Errors: 9, naming the offender, launching nothing and leaving the snapshot
+ *   usable, for everything yb_gpu_snapshot_query rejects in a predicate, a
+ *   projected string or out-of-range column, num_cols == 0 and num_cols over
+ *   YBG_MAX_SELECT_COLS. 8 when cap is smaller than the number of rows to
+ *   deliver (out->n_rows then holds the count needed; the other counters
+ *   are filled). 10 device.
+ * An empty snapshot or an empty window launches nothing and returns zero
+ *   rows with done = 1.
+ * Memory: the first select allocates the snapshot's select scratch (match
+ *   bitmap, per-tile counts and offsets) and its device output buffers, the
+ *   latter grown on demand; ybg_snapshot_info_t.device_bytes includes them
+ *   from then on.
+ * yb_gpu_snapshot_kernel_ms then reports count + scan + gather. */
+int yb_gpu_snapshot_select(ybg_snapshot_t *sn, const ybg_snapshot_select_t *q,
+                           uint64_t *datums, uint32_t *null_masks, uint64_t *row_ids,
+                           uint64_t cap, ybg_snapshot_select_result_t *out);
+/* Rows per compaction tile of the select kernels (tests derive edges from
+ * it). */
+uint64_t ybg_snapshot_select_tile_rows(void);
+
 /* Device time (events) of the last query: query kernel + final reduce. */
 int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t *sn, double *query_ms);
 int yb_gpu_snapshot_close(ybg_snapshot_t *sn);

@@ -655,6 +655,108 @@ def sim_snapshot_group_query(spec, data, offsets, n_blocks, preds, aggs,
     return groups, (keys, vals, cnts), res
 
 
+MAX_SELECT_COLS = MAX_COLS + MAX_KEYCOLS
+ROW_END = 2**64 - 1
+
+
+class SelectCol(C.Structure):
+    """ybg_select_col_t."""
+    _fields_ = [("is_key_col", C.c_int32), ("col", C.c_int32)]
+
+
+class SnapshotSelect(C.Structure):
+    """ybg_snapshot_select_t."""
+    _fields_ = [("num_preds", C.c_int32), ("preds", Pred * MAX_PREDS),
+                ("num_cols", C.c_int32),
+                ("cols", SelectCol * MAX_SELECT_COLS),
+                ("backward", C.c_int32),
+                ("row_lo", C.c_uint64), ("row_hi", C.c_uint64),
+                ("row_limit", C.c_uint64)]
+
+
+class SnapshotSelectResult(C.Structure):
+    """ybg_snapshot_select_result_t."""
+    _fields_ = [("n_rows", C.c_uint64), ("rows_scanned", C.c_uint64),
+                ("rows_matched", C.c_uint64), ("resume_row", C.c_uint64),
+                ("done", C.c_int32), ("entries_seen", C.c_uint64),
+                ("restart_ht", C.c_uint8 * MAX_HT),
+                ("restart_ht_len", C.c_uint32)]
+
+
+def snapshot_select(preds, cols, limit=0, backward=False, row_lo=0,
+                    row_hi=None):
+    """Pack a snapshot select. cols: (is_key_col, col) pairs or SelectCol.
+    Counts over the caps pass through (the ABI answers them with code 9);
+    row_hi None = to the end."""
+    q = SnapshotSelect()
+    q.num_preds = len(preds)
+    for i, p in enumerate(preds[:MAX_PREDS]):
+        q.preds[i] = p
+    q.num_cols = len(cols)
+    for i, c in enumerate(cols[:MAX_SELECT_COLS]):
+        q.cols[i] = c if isinstance(c, SelectCol) else \
+            SelectCol(1 if c[0] else 0, c[1])
+    q.backward = 1 if backward else 0
+    q.row_lo = row_lo
+    q.row_hi = ROW_END if row_hi is None else row_hi
+    q.row_limit = limit
+    return q
+
+
+def snapshot_select_tile_rows():
+    """Rows per compaction tile of the select kernels
+    (ybg_snapshot_select_tile_rows)."""
+    return _sig(product(), "ybg_snapshot_select_tile_rows", C.c_uint64, [])()
+
+
+def decode_snapshot_rows(res, datums, null_masks, num_cols, cols, cap):
+    """Select output -> [(projected values..., None for NULL)], one tuple
+    per delivered row in delivery order. cols: the (is_key_col, col) pairs
+    of the projection; cap: the capacity the arrays were passed with."""
+    cols = [(c.is_key_col, c.col) if isinstance(c, SelectCol) else c
+            for c in cols]
+    n = res.n_rows
+    by_col = [datums[j * cap:j * cap + n] for j in range(num_cols)]
+    rows = list(zip(*by_col))
+    for i, nm in enumerate(null_masks[:n]):
+        if nm:
+            rows[i] = tuple(
+                None if (not cols[j][0] and (nm >> cols[j][1]) & 1)
+                else rows[i][j] for j in range(num_cols))
+    return rows
+
+
+def sim_snapshot_select(spec, data, offsets, n_blocks, preds, cols, limit=0,
+                        backward=False, row_lo=0, row_hi=None, cap=1 << 16):
+    """Host SIMULATOR of the snapshot select (ybg_sim_snapshot_select) —
+    TEST INFRASTRUCTURE: the snapshot layout built as in sim_snapshot_query,
+    then the device bit packing / rank / gather code one simulated tile at a
+    time. Returns ((datums, null_masks, row_ids) raw ctypes arrays, result
+    struct); raises RuntimeError carrying .code and .result on a non-zero
+    code."""
+    lib = product()
+    f = _sig(lib, "ybg_sim_snapshot_select", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(SnapshotSelect),
+              C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+              C.POINTER(C.c_uint64), C.c_uint64,
+              C.POINTER(SnapshotSelectResult)])
+    q = snapshot_select(preds, cols, limit, backward, row_lo, row_hi)
+    n = max(cap, 1)
+    datums = (C.c_uint64 * (n * max(1, min(len(cols), MAX_SELECT_COLS))))()
+    null_masks = (C.c_uint32 * n)()
+    row_ids = (C.c_uint64 * n)()
+    res = SnapshotSelectResult()
+    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), datums,
+           null_masks, row_ids, cap, C.byref(res))
+    if rc != 0:
+        err = RuntimeError(f"ybg_sim_snapshot_select failed rc={rc}")
+        err.code = rc
+        err.result = res
+        raise err
+    return (datums, null_masks, row_ids), res
+
+
 def sim_scan_fast(spec, data, offsets, n_blocks):
     """Host simulator of the SPECIALIZED fast batch scanner
     (scan_batch_fast + general fallback per aborted batch) — TEST

@@ -697,3 +697,131 @@ int ybg_sim_snapshot_group_query(const ybg_scan_spec_t* spec,
 }
 
 }  // extern "C"
+
+namespace {
+
+// k_snap_select_count, one simulated tile at a time: the lanes' two row
+// slots become the wave ballots, packed into the tile's bitmap words by the
+// shared code.
+template <bool NULLS, bool GEN>
+void sim_select_count(const SnapQuery& q, const SnapWindow& win,
+                      uint64_t* bitmap, uint64_t* tile_cnt) {
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    const uint64_t tile = win.tile_lo + t;
+    uint64_t cnt = 0;  // one 16-bit count per wave
+    for (int wave = 0; wave < kSnapThreads / 64; ++wave) {
+      uint64_t b[kSnapVec] = {0, 0};
+      for (int lane = 0; lane < 64; ++lane) {
+        const uint64_t r0 =
+            tile * kSnapTileRows + (uint64_t)(wave * 64 + lane) * kSnapVec;
+        const bool ld = r0 < win.hi && r0 + kSnapVec > win.lo;
+        for (int k = 0; k < kSnapVec; ++k) {
+          const uint64_t r = r0 + k;
+          uint64_t pv[YBG_MAX_PREDS] = {0};
+          if (ld)
+            for (int i = 0; i < q.num_preds; ++i) pv[i] = q.preds[i].col[r];
+          const bool m = snap_pred_pass<YBG_MAX_PREDS, NULLS, GEN>(
+              q, pv, (NULLS && ld) ? q.nullmask[r] : 0u,
+              r >= win.lo && r < win.hi);
+          if (m) b[k] |= 1ull << lane;
+        }
+      }
+      snap_select_pack(b[0], b[1], bitmap + tile * kSnapTileWords + wave * 2);
+      cnt |= (uint64_t)(snap_popc64(b[0]) + snap_popc64(b[1]))
+             << (16 * wave);
+    }
+    tile_cnt[t] = cnt;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The tile width the simulator walks (= ybg_snapshot_select_tile_rows; the
+// stand-alone driver links no device code).
+uint64_t ybg_sim_snapshot_select_tile_rows(void) { return kSnapTileRows; }
+
+// Select simulator: yb_gpu_snapshot_select's contract (codes 8 / 9
+// included) from the same translation, bit packing, rank, output index and
+// emit code, the tiles walked serially.
+int ybg_sim_snapshot_select(const ybg_scan_spec_t* spec, const uint8_t* data,
+                            const uint64_t* offsets, uint64_t n_blocks,
+                            const ybg_snapshot_select_t* query,
+                            uint64_t* datums, uint32_t* null_masks,
+                            uint64_t* row_ids, uint64_t cap,
+                            ybg_snapshot_select_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  SimSnapshot snap;
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  if (rc) return rc;
+  const uint64_t n_rows = snap.n;
+  SnapQuery q;
+  SnapSelect sel;
+  std::vector<uint8_t> aux;
+  char err[192];
+  rc = snap_build_select(spec->schema, &snap.cols, *query, n_rows, &aux, &q,
+                         &sel, err, sizeof(err));
+  if (rc) return rc;
+  q.aux = aux.data();
+  out->entries_seen = snap.stats.entries_seen;
+  memcpy(out->restart_ht, snap.stats.restart_ht, snap.stats.restart_ht_len);
+  out->restart_ht_len = snap.stats.restart_ht_len;
+  const uint64_t hi = query->row_hi < n_rows ? query->row_hi : n_rows;
+  const uint64_t lo = query->row_lo;
+  SnapSelectHdr h = {0, 0, 0};
+  if (lo >= hi) {
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    return 0;
+  }
+  const SnapWindow win = snap_select_window(lo, hi);
+  const uint64_t tiles = (n_rows + kSnapTileRows - 1) / kSnapTileRows;
+  std::vector<uint64_t> bitmap(tiles * kSnapTileWords, 0);
+  std::vector<uint64_t> tile_cnt(win.n_tiles);
+  std::vector<uint32_t> tile_off(win.n_tiles);
+  const int v = (q.any_nullable ? 2 : 0) | (q.general ? 1 : 0);
+  switch (v) {
+    case 0: sim_select_count<false, false>(q, win, bitmap.data(),
+                                           tile_cnt.data()); break;
+    case 1: sim_select_count<false, true>(q, win, bitmap.data(),
+                                          tile_cnt.data()); break;
+    case 2: sim_select_count<true, false>(q, win, bitmap.data(),
+                                          tile_cnt.data()); break;
+    default: sim_select_count<true, true>(q, win, bitmap.data(),
+                                          tile_cnt.data()); break;
+  }
+  // k_snap_select_scan, serially
+  uint64_t total = 0;
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    tile_off[t] = (uint32_t)total;
+    total += snap_select_tile_count(tile_cnt[t]);
+  }
+  snap_select_range(total, query->row_limit, sel.backward, &h);
+  const uint64_t n = h.end - h.first;
+  if (n > cap) {
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    out->done = 0;
+    out->resume_row = 0;
+    return 8;
+  }
+  if (n == 0) {
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    return 0;
+  }
+  // k_snap_select_gather: straight into the caller's arrays (pitch cap)
+  const SnapSelectOut so = {row_ids, null_masks, datums, cap};
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    const uint64_t off = tile_off[t];
+    const uint64_t cnt = snap_select_tile_count(tile_cnt[t]);
+    if (cnt == 0 || off + cnt <= h.first || off >= h.end) continue;
+    const uint64_t tile = win.tile_lo + t;
+    for (uint32_t lane = 0; lane < (uint32_t)kSnapThreads; ++lane)
+      snap_select_gather_pair(sel, so, h, bitmap.data() + tile * kSnapTileWords,
+                              tile, off, lane * kSnapVec);
+  }
+  snap_select_fill(lo, hi, h, sel.backward, row_ids[n - 1], row_ids[n - 1],
+                   out);
+  return 0;
+}
+
+}  // extern "C"

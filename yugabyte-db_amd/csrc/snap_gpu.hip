@@ -20,6 +20,10 @@
 //    workgroup-local LDS table flushed into the snapshot's global group
 //    table (or straight into it); k_snap_group_init / _compact / _export
 //    reset the table and deliver the groups ordered by key.
+//  * k_snap_select_count / _scan / _gather: SELECT — the matching rows in
+//    key order as an ordered stream compaction in three launches (per-tile
+//    match bitmap + counts, one-workgroup prefix sum, rank and gather of the
+//    projected columns); no workgroup waits on another.
 //  The grid is a pure function of n_rows, so together with the sorted
 //  build, results (double SUM included) are bit-identical across queries
 //  and across separately built snapshots of the same tablet.
@@ -318,6 +322,152 @@ __global__ __launch_bounds__(256) void k_snap_group_export(
 }
 
 // ---------------------------------------------------------------------------
+// SELECT: count / scan / gather (snap_device.h has the per-tile logic).
+// ---------------------------------------------------------------------------
+
+// Workgroup w walks the window's tiles w, w + gridDim.x, ...: k_snap_query's
+// load shape (two rows per lane, one 16-byte load per predicate column, all
+// loads before any compare) on a contiguous tile. Tiles are kSnapTileRows-
+// aligned whatever the window, so the pair loads stay 16-byte aligned; rows
+// outside [lo, hi) are masked out of the fold. Each wave packs its two
+// ballots into two bitmap words and writes its match count into its own
+// 16-bit lane of the tile's count word: no LDS, no barrier.
+template <int NP, bool NULLS, bool GEN>
+__global__ __launch_bounds__(kSnapThreads) void k_snap_select_count(
+    SnapQuery q, SnapWindow win, unsigned long long* __restrict__ bitmap,
+    unsigned long long* __restrict__ tile_cnt) {
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (uint64_t t = blockIdx.x; t < win.n_tiles; t += gridDim.x) {
+    const uint64_t tile = win.tile_lo + t;
+    const uint64_t r0 = tile * kSnapTileRows + threadIdx.x * kSnapVec;
+    // the pair intersects the window (hi <= n_rows: inside the allocation)
+    const bool ld = r0 < win.hi && r0 + kSnapVec > win.lo;
+    snap_u64x2 pv[NP];
+    snap_u32x2 nm = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      pv[i] = snap_u64x2{0ull, 0ull};
+      if (ld && i < q.num_preds)
+        pv[i] = *reinterpret_cast<const snap_u64x2*>(q.preds[i].col + r0);
+    }
+    if (NULLS && ld) nm = *reinterpret_cast<const snap_u32x2*>(q.nullmask + r0);
+    uint64_t p0[NP], p1[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { p0[i] = pv[i].x; p1[i] = pv[i].y; }
+    const bool m0 = snap_pred_pass<NP, NULLS, GEN>(
+        q, p0, nm.x, r0 >= win.lo && r0 < win.hi);
+    const bool m1 = snap_pred_pass<NP, NULLS, GEN>(
+        q, p1, nm.y, r0 + 1 >= win.lo && r0 + 1 < win.hi);
+    const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
+    if (lane == 0) {
+      uint64_t w[2];
+      snap_select_pack(b0, b1, w);
+      *reinterpret_cast<snap_u64x2*>(bitmap + tile * kSnapTileWords +
+                                     wave * 2) = snap_u64x2{w[0], w[1]};
+      reinterpret_cast<uint16_t*>(tile_cnt + t)[wave] =
+          (uint16_t)(__popcll(b0) + __popcll(b1));
+    }
+  }
+}
+
+// One workgroup: rounds of kSnapScanThreads x kSnapScanVec tile counts in
+// tile order, lanes adjacent in memory. Each thread folds its kSnapScanVec
+// counts, lanes scan by 32-bit shuffles (a round holds < 2^32 matches), wave
+// totals go through LDS (two sets, so one barrier per round), the running
+// carry stays in a register. The next round's count words are loaded before
+// the current round is folded. n_slots = snap_select_tile_slots(n_tiles);
+// words past n_tiles are stale and masked.
+__global__ __launch_bounds__(kSnapScanThreads) void k_snap_select_scan(
+    const unsigned long long* __restrict__ tile_cnt,
+    uint32_t* __restrict__ tile_off, uint64_t n_tiles, uint64_t n_slots,
+    uint64_t limit, int backward, SnapSelectHdr* __restrict__ hdr) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  static_assert(kSnapScanVec == 4, "two 16-byte loads, one 16-byte store");
+  constexpr int kWaves = kSnapScanThreads / 64;
+  constexpr uint64_t kRound = (uint64_t)kSnapScanThreads * kSnapScanVec;
+  __shared__ uint32_t wave_tot[2][kWaves];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t mine0 = (uint64_t)threadIdx.x * kSnapScanVec;
+  snap_u64x2 cur[2] = {{0ull, 0ull}, {0ull, 0ull}}, nxt[2];
+  if (mine0 < n_slots) {
+    cur[0] = *reinterpret_cast<const snap_u64x2*>(tile_cnt + mine0);
+    cur[1] = *reinterpret_cast<const snap_u64x2*>(tile_cnt + mine0 + 2);
+  }
+  uint64_t carry = 0;
+  unsigned par = 0;
+  for (uint64_t base = 0; base < n_slots; base += kRound, par ^= 1) {
+    const uint64_t i = base + mine0;
+    nxt[0] = nxt[1] = snap_u64x2{0ull, 0ull};
+    if (i + kRound < n_slots) {
+      nxt[0] = *reinterpret_cast<const snap_u64x2*>(tile_cnt + i + kRound);
+      nxt[1] = *reinterpret_cast<const snap_u64x2*>(tile_cnt + i + kRound + 2);
+    }
+    const uint32_t c0 = i + 0 < n_tiles ? snap_select_tile_count(cur[0].x) : 0u;
+    const uint32_t c1 = i + 1 < n_tiles ? snap_select_tile_count(cur[0].y) : 0u;
+    const uint32_t c2 = i + 2 < n_tiles ? snap_select_tile_count(cur[1].x) : 0u;
+    const uint32_t c3 = i + 3 < n_tiles ? snap_select_tile_count(cur[1].y) : 0u;
+    const uint32_t mine = c0 + c1 + c2 + c3;
+    uint32_t incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t up = __shfl_up(incl, off);
+      if (lane >= (unsigned)off) incl += up;
+    }
+    if (lane == 63) wave_tot[par][wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, round = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      const uint32_t wt = wave_tot[par][w];
+      if (w < (int)wave) before += wt;
+      round += wt;
+    }
+    if (i < n_slots) {
+      u32x4 o;
+      o.x = (uint32_t)carry + before + incl - mine;
+      o.y = o.x + c0;
+      o.z = o.y + c1;
+      o.w = o.z + c2;
+      *reinterpret_cast<u32x4*>(tile_off + i) = o;
+    }
+    carry += round;
+    cur[0] = nxt[0];
+    cur[1] = nxt[1];
+  }
+  if (threadIdx.x == 0) {
+    SnapSelectHdr h;
+    snap_select_range(carry, limit, backward, &h);
+    *hdr = h;
+  }
+}
+
+// Workgroup w walks the same tiles as the count pass and re-reads only their
+// bitmap words (uniform across the workgroup) — no predicate column, no
+// barrier. Lane l owns bits 2l and 2l + 1 of its tile; consecutive ranks go
+// to consecutive output addresses.
+__global__ __launch_bounds__(kSnapThreads) void k_snap_select_gather(
+    SnapSelect s, SnapSelectOut o, SnapWindow win,
+    const unsigned long long* __restrict__ bitmap,
+    const unsigned long long* __restrict__ tile_cnt,
+    const uint32_t* __restrict__ tile_off,
+    const SnapSelectHdr* __restrict__ hdr) {
+  const SnapSelectHdr h = *hdr;
+  for (uint64_t t = blockIdx.x; t < win.n_tiles; t += gridDim.x) {
+    const uint64_t off = tile_off[t];
+    const uint64_t cnt = snap_select_tile_count(tile_cnt[t]);
+    // no match, or every rank of the tile outside the delivered range
+    if (cnt == 0 || off + cnt <= h.first || off >= h.end) continue;
+    const uint64_t tile = win.tile_lo + t;
+    uint64_t words[kSnapTileWords];
+#pragma unroll
+    for (int w = 0; w < kSnapTileWords; ++w)
+      words[w] = bitmap[tile * kSnapTileWords + w];
+    snap_select_gather_pair(s, o, h, words, tile, off,
+                            threadIdx.x * kSnapVec);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Build kernels
 // ---------------------------------------------------------------------------
 
@@ -415,6 +565,17 @@ struct ybg_snapshot {
   long long* d_gout_vals = nullptr;
   unsigned long long* d_gout_cnts = nullptr;
   uint64_t gout_cap = 0;
+  // select: scratch sized by n_rows and allocated by the first select, the
+  // device output buffers grown on demand (device_bytes counts all of them)
+  hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around the gather
+  unsigned long long* d_sel_bitmap = nullptr;   // [tiles * kSnapTileWords]
+  unsigned long long* d_sel_cnt = nullptr;      // [snap_select_tile_slots]
+  uint32_t* d_sel_off = nullptr;                // [snap_select_tile_slots]
+  SnapSelectHdr* d_sel_hdr = nullptr;
+  uint64_t* d_sel_rowids = nullptr;             // [sel_cap]
+  uint32_t* d_sel_nulls = nullptr;              // [sel_cap]
+  uint64_t* d_sel_datums = nullptr;             // [sel_cols * sel_cap]
+  uint64_t sel_cap = 0, sel_cols = 0;
 };
 
 namespace {
@@ -434,6 +595,13 @@ void snap_free(ybg_snapshot* sn) {
                      sn->d_gout_vals, sn->d_gout_cnts};
   for (void* p : grouped)
     if (p) HIP_WARN(hipFree(p));
+  void* select[] = {sn->d_sel_bitmap, sn->d_sel_cnt, sn->d_sel_off,
+                    sn->d_sel_hdr, sn->d_sel_rowids, sn->d_sel_nulls,
+                    sn->d_sel_datums};
+  for (void* p : select)
+    if (p) HIP_WARN(hipFree(p));
+  if (sn->ev_s0) HIP_WARN(hipEventDestroy(sn->ev_s0));
+  if (sn->ev_s1) HIP_WARN(hipEventDestroy(sn->ev_s1));
   if (sn->ev_q0) HIP_WARN(hipEventDestroy(sn->ev_q0));
   if (sn->ev_q1) HIP_WARN(hipEventDestroy(sn->ev_q1));
   if (sn->stream) HIP_WARN(hipStreamDestroy(sn->stream));
@@ -763,6 +931,153 @@ int snap_group_query(ybg_snapshot* sn, const ybg_snapshot_group_query_t* gqa,
   return 0;
 }
 
+// ---- select -----------------------------------------------------------------
+
+template <int NP, bool GEN>
+void snap_select_launch_count(const SnapQuery& q, const SnapWindow& win,
+                              int grid, hipStream_t st,
+                              unsigned long long* bitmap,
+                              unsigned long long* cnt) {
+  if (q.any_nullable)
+    hipLaunchKernelGGL((k_snap_select_count<NP, true, GEN>), dim3(grid),
+                       dim3(kSnapThreads), 0, st, q, win, bitmap, cnt);
+  else
+    hipLaunchKernelGGL((k_snap_select_count<NP, false, GEN>), dim3(grid),
+                       dim3(kSnapThreads), 0, st, q, win, bitmap, cnt);
+}
+
+// First select: the bitmap, the tile arrays and the header.
+int snap_select_ensure_scratch(ybg_snapshot* sn) {
+  const uint64_t tiles = (sn->n_rows + kSnapTileRows - 1) / kSnapTileRows;
+  const uint64_t slots = snap_select_tile_slots(tiles);
+  int rc = 0;
+  if (!sn->ev_s0) HIP_TRY(hipEventCreate(&sn->ev_s0));
+  if (!sn->ev_s1) HIP_TRY(hipEventCreate(&sn->ev_s1));
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_bitmap,
+                             tiles * kSnapTileWords * 8)))
+    return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_cnt, slots * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_off, slots * 4))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_hdr, sizeof(SnapSelectHdr))))
+    return rc;
+  return 0;
+}
+
+// Device output buffers for n rows of ncols projected columns.
+int snap_select_ensure_out(ybg_snapshot* sn, uint64_t n, uint64_t ncols) {
+  if (n <= sn->sel_cap && ncols <= sn->sel_cols) return 0;
+  void* old[] = {sn->d_sel_rowids, sn->d_sel_nulls, sn->d_sel_datums};
+  for (void* p : old)
+    if (p) HIP_WARN(hipFree(p));
+  sn->d_sel_rowids = nullptr;
+  sn->d_sel_nulls = nullptr;
+  sn->d_sel_datums = nullptr;
+  sn->device_bytes -= sn->sel_cap * (8 + 4 + 8 * sn->sel_cols);
+  uint64_t want = sn->sel_cap > 1024 ? sn->sel_cap : 1024;
+  while (want < n) want <<= 1;
+  const uint64_t wcols = ncols > sn->sel_cols ? ncols : sn->sel_cols;
+  sn->sel_cap = 0;
+  sn->sel_cols = 0;
+  int rc = 0;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_rowids, want * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_nulls, want * 4))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_sel_datums, want * 8 * wcols)))
+    return rc;
+  sn->sel_cap = want;
+  sn->sel_cols = wcols;
+  return 0;
+}
+
+int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
+                uint64_t* datums, uint32_t* null_masks, uint64_t* row_ids,
+                uint64_t cap, ybg_snapshot_select_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  const SnapCols cols = snap_cols(sn);
+  SnapQuery q;
+  SnapSelect sel;
+  char err[192];
+  // a launched plain query may still read aux_host / d_aux
+  if (sn->pending) HIP_TRY(hipStreamSynchronize(sn->stream));
+  sn->aux_host.clear();
+  int rc = snap_build_select(sn->schema, &cols, *sq, sn->n_rows,
+                             &sn->aux_host, &q, &sel, err, sizeof(err));
+  if (rc) return set_err(rc, err);
+  out->entries_seen = sn->entries_seen;
+  memcpy(out->restart_ht, sn->restart_ht, sn->restart_len);
+  out->restart_ht_len = sn->restart_len;
+  sn->last_query_ms = 0;
+  const uint64_t hi = sq->row_hi < sn->n_rows ? sq->row_hi : sn->n_rows;
+  const uint64_t lo = sq->row_lo;
+  SnapSelectHdr h = {0, 0, 0};
+  if (lo >= hi) {  // empty snapshot or window: nothing launched
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    return 0;
+  }
+
+  if ((rc = snap_select_ensure_scratch(sn))) return rc;
+  if ((rc = snap_upload_aux(sn, &q))) return rc;
+  const SnapWindow win = snap_select_window(lo, hi);
+  const int grid =
+      (int)(win.n_tiles < kSnapMaxGrid ? win.n_tiles : kSnapMaxGrid);
+  HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+  if (q.general)
+    snap_select_launch_count<8, true>(q, win, grid, sn->stream,
+                                      sn->d_sel_bitmap, sn->d_sel_cnt);
+  else if (q.num_preds <= 4)
+    snap_select_launch_count<4, false>(q, win, grid, sn->stream,
+                                       sn->d_sel_bitmap, sn->d_sel_cnt);
+  else
+    snap_select_launch_count<8, false>(q, win, grid, sn->stream,
+                                       sn->d_sel_bitmap, sn->d_sel_cnt);
+  hipLaunchKernelGGL(k_snap_select_scan, dim3(1), dim3(kSnapScanThreads), 0,
+                     sn->stream, sn->d_sel_cnt, sn->d_sel_off, win.n_tiles,
+                     snap_select_tile_slots(win.n_tiles), sq->row_limit,
+                     sel.backward, sn->d_sel_hdr);
+  HIP_TRY(hipEventRecord(sn->ev_q1, sn->stream));
+  // the delivered count sizes the output buffers and the copies
+  HIP_TRY(hipMemcpyAsync(&h, sn->d_sel_hdr, sizeof(h), hipMemcpyDeviceToHost,
+                         sn->stream));
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  const uint64_t n = h.end - h.first;
+  float ms = 0, ms2 = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, sn->ev_q0, sn->ev_q1));
+  sn->last_query_ms = ms;
+  if (n > cap) {
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    out->done = 0;
+    out->resume_row = 0;
+    return set_err(8, "snapshot select: " + std::to_string(n) +
+                          " rows exceed the output capacity " +
+                          std::to_string(cap));
+  }
+  if (n == 0) {
+    snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+    return 0;
+  }
+  if ((rc = snap_select_ensure_out(sn, n, (uint64_t)sel.num_cols))) return rc;
+  const SnapSelectOut so = {sn->d_sel_rowids, sn->d_sel_nulls,
+                            sn->d_sel_datums, sn->sel_cap};
+  HIP_TRY(hipEventRecord(sn->ev_s0, sn->stream));
+  hipLaunchKernelGGL(k_snap_select_gather, dim3(grid), dim3(kSnapThreads), 0,
+                     sn->stream, sel, so, win, sn->d_sel_bitmap,
+                     sn->d_sel_cnt, sn->d_sel_off, sn->d_sel_hdr);
+  HIP_TRY(hipEventRecord(sn->ev_s1, sn->stream));
+  HIP_TRY(hipMemcpyAsync(row_ids, sn->d_sel_rowids, n * 8,
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipMemcpyAsync(null_masks, sn->d_sel_nulls, n * 4,
+                         hipMemcpyDeviceToHost, sn->stream));
+  // column j: n datums from device pitch sel_cap to the caller's pitch cap
+  HIP_TRY(hipMemcpy2DAsync(datums, cap * 8, sn->d_sel_datums,
+                           sn->sel_cap * 8, n * 8, (size_t)sel.num_cols,
+                           hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  HIP_TRY(hipEventElapsedTime(&ms2, sn->ev_s0, sn->ev_s1));
+  sn->last_query_ms = (double)ms + ms2;
+  snap_select_fill(lo, hi, h, sel.backward, row_ids[n - 1], row_ids[n - 1],
+                   out);
+  return 0;
+}
+
 }  // namespace
 
 namespace ybgint {
@@ -1020,6 +1335,15 @@ int yb_gpu_snapshot_group_query(ybg_snapshot_t* sn,
                                 ybg_snapshot_group_result_t* out) {
   return snap_group_query(sn, q, keys, vals, cnts, cap, out);
 }
+
+int yb_gpu_snapshot_select(ybg_snapshot_t* sn, const ybg_snapshot_select_t* q,
+                           uint64_t* datums, uint32_t* null_masks,
+                           uint64_t* row_ids, uint64_t cap,
+                           ybg_snapshot_select_result_t* out) {
+  return snap_select(sn, q, datums, null_masks, row_ids, cap, out);
+}
+
+uint64_t ybg_snapshot_select_tile_rows(void) { return kSnapTileRows; }
 
 uint64_t ybg_snapshot_group_local_slots(int32_t num_aggs) {
   return (uint64_t)snap_group_local_slots(snap_group_na(num_aggs));

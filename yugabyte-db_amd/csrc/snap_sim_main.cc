@@ -8,7 +8,12 @@
 // runs over the same table at both levels (workgroup-local table + flush,
 // global table only), grouped on the int32 value column, and is
 // cross-checked against the block-path GROUP BY simulator (ybg_sim_group).
+// The select runs over the same table plus the sizes around its tile width
+// — unlimited, limited, backward and odd-window variants — and is
+// cross-checked against the block-path emit simulator (ybg_sim_emit, rows
+// ordered by sort_key).
 // TEST INFRASTRUCTURE; not linked into the product library.
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -31,6 +36,16 @@ extern "C" int ybg_sim_group(const ybg_scan_spec_t*, const uint8_t*,
                              const uint64_t*, uint64_t, uint64_t*, long long*,
                              unsigned long long*, uint8_t*, uint64_t,
                              uint64_t, uint64_t*, uint8_t*, uint32_t*);
+
+extern "C" int ybg_sim_snapshot_select(
+    const ybg_scan_spec_t*, const uint8_t*, const uint64_t*, uint64_t,
+    const ybg_snapshot_select_t*, uint64_t*, uint32_t*, uint64_t*, uint64_t,
+    ybg_snapshot_select_result_t*);
+extern "C" uint64_t ybg_sim_snapshot_select_tile_rows(void);
+extern "C" int ybg_sim_emit(const ybg_scan_spec_t*, const uint8_t*,
+                            const uint64_t*, uint64_t, uint64_t, uint64_t*,
+                            uint64_t*, uint64_t*, uint32_t*, uint8_t*,
+                            uint64_t, uint64_t*, uint64_t*);
 
 namespace {
 
@@ -99,6 +114,131 @@ int check_grouped(ybg_scan_spec_t spec, const uint8_t* data,
   return bad;
 }
 
+// One emitted row of the block path, keyed by its tablet position.
+struct EmitRow {
+  uint64_t sort_key, key0, val[3];
+  uint32_t nm;
+};
+
+int emit_rows(const ybg_scan_spec_t& spec, const uint8_t* data,
+              const uint64_t* offsets, uint64_t n_blocks, uint64_t cap,
+              std::vector<EmitRow>* out) {
+  cap = cap ? cap : 1;
+  std::vector<uint64_t> sk(cap), kd(cap), dat(cap * 3);
+  std::vector<uint32_t> nm(cap);
+  uint64_t n = 0, vl = 0;
+  int rc = ybg_sim_emit(&spec, data, offsets, n_blocks, cap, sk.data(),
+                        kd.data(), dat.data(), nm.data(), nullptr, 0, &n, &vl);
+  if (rc) return rc;
+  out->resize(n);
+  for (uint64_t i = 0; i < n; ++i)
+    (*out)[i] = EmitRow{sk[i], kd[i], {dat[i * 3], dat[i * 3 + 1],
+                                       dat[i * 3 + 2]}, nm[i]};
+  std::sort(out->begin(), out->end(),
+            [](const EmitRow& a, const EmitRow& b) {
+              return a.sort_key < b.sort_key;
+            });
+  return 0;
+}
+
+// The select over (spec's tablet, q's predicates), projecting the key, the
+// three value columns and the nullable double once more, against the block
+// path's emitted rows: positions from the unfiltered emit, the expected page
+// from the filtered one.
+int check_select(ybg_scan_spec_t spec, const uint8_t* data,
+                 const uint64_t* offsets, uint64_t n_blocks, uint64_t n,
+                 const ybg_snapshot_query_t& q) {
+  ybg_scan_spec_t bs = spec;
+  bs.num_preds = 0;
+  bs.num_aggs = 0;
+  spec.num_aggs = 0;
+  std::vector<EmitRow> all, match;
+  int bad = emit_rows(bs, data, offsets, n_blocks, n, &all) ||
+            emit_rows(spec, data, offsets, n_blocks, n, &match);
+  if (bad) return bad;
+  std::vector<uint64_t> all_keys(all.size());
+  for (size_t i = 0; i < all.size(); ++i) all_keys[i] = all[i].sort_key;
+  const uint64_t n_rows = all.size();
+
+  ybg_snapshot_select_t sq;
+  memset(&sq, 0, sizeof(sq));
+  sq.num_preds = q.num_preds;
+  memcpy(sq.preds, q.preds, sizeof(sq.preds));
+  sq.num_cols = 5;
+  sq.cols[0] = {1, 0};
+  sq.cols[1] = {0, 0};
+  sq.cols[2] = {0, 1};
+  sq.cols[3] = {0, 2};
+  sq.cols[4] = {0, 1};
+  const uint64_t tile = ybg_sim_snapshot_select_tile_rows();
+  struct Variant {
+    uint64_t lo, hi, limit;
+    int backward;
+  };
+  const Variant variants[] = {
+      {0, UINT64_MAX, 0, 0},           {0, UINT64_MAX, 5, 0},
+      {0, UINT64_MAX, 0, 1},           {0, UINT64_MAX, 5, 1},
+      {1, n_rows | 1, 0, 0},           {3, n_rows > 4 ? n_rows - 2 : 3, 7, 1},
+      {tile - 1, tile + 2, 0, 0},      {tile + 1, 2 * tile - 1, 3, 1},
+      {n_rows, UINT64_MAX, 0, 0}};
+  const uint64_t cap = n_rows + 1;
+  std::vector<uint64_t> datums(cap * 5), ids(cap);
+  std::vector<uint32_t> nms(cap);
+  for (const Variant& v : variants) {
+    sq.row_lo = v.lo;
+    sq.row_hi = v.hi;
+    sq.row_limit = v.limit;
+    sq.backward = v.backward;
+    ybg_snapshot_select_result_t res;
+    int rc = ybg_sim_snapshot_select(&bs, data, offsets, n_blocks, &sq,
+                                     datums.data(), nms.data(), ids.data(),
+                                     cap, &res);
+    const uint64_t hi = v.hi < n_rows ? v.hi : n_rows;
+    std::vector<std::pair<uint64_t, const EmitRow*>> want;  // (position, row)
+    for (const EmitRow& r : match) {
+      const uint64_t pos =
+          std::lower_bound(all_keys.begin(), all_keys.end(), r.sort_key) -
+          all_keys.begin();
+      if (pos >= v.lo && pos < hi) want.emplace_back(pos, &r);
+    }
+    const uint64_t total = want.size();
+    if (v.backward) std::reverse(want.begin(), want.end());
+    if (v.limit && want.size() > v.limit) want.resize(v.limit);
+    int lbad = rc || res.n_rows != want.size() || res.rows_matched != total ||
+               res.rows_scanned != (hi > v.lo ? hi - v.lo : 0) ||
+               res.done != (want.size() == total ? 1 : 0);
+    if (!lbad) {
+      uint64_t resume = v.backward ? v.lo : hi;
+      if (!res.done)
+        resume = v.backward ? want.back().first : want.back().first + 1;
+      lbad = res.resume_row != resume;
+    }
+    for (uint64_t i = 0; i < want.size() && !lbad; ++i) {
+      const EmitRow& r = *want[i].second;
+      const uint32_t nm = r.nm & 0x7u;
+      const uint64_t exp[5] = {r.key0, (nm & 1) ? 0 : r.val[0],
+                               (nm & 2) ? 0 : r.val[1],
+                               (nm & 4) ? 0 : r.val[2],
+                               (nm & 2) ? 0 : r.val[1]};
+      lbad = ids[i] != want[i].first || nms[i] != nm;
+      for (int j = 0; j < 5 && !lbad; ++j)
+        lbad = datums[(uint64_t)j * cap + i] != exp[j];
+    }
+    if (lbad)
+      printf("  select lo=%llu hi=%llu limit=%llu backward=%d: rows=%llu "
+             "matched=%llu MISMATCH\n",
+             (unsigned long long)v.lo, (unsigned long long)v.hi,
+             (unsigned long long)v.limit, v.backward,
+             (unsigned long long)res.n_rows,
+             (unsigned long long)res.rows_matched);
+    bad |= lbad;
+  }
+  printf("  select: %zu variants, %zu of %llu rows match %s\n",
+         sizeof(variants) / sizeof(variants[0]), match.size(),
+         (unsigned long long)n_rows, bad ? "MISMATCH" : "ok");
+  return bad;
+}
+
 int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
               const ybg_snapshot_query_t& q, bool nulls) {
   ybg_builder_t* b =
@@ -152,6 +292,7 @@ int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
          (unsigned long long)snap.rows_scanned,
          (unsigned long long)snap.rows_matched, bad ? "MISMATCH" : "ok");
   bad |= check_grouped(spec, data, offsets, n_blocks, q);
+  bad |= check_select(spec, data, offsets, n_blocks, n, q);
   ybg_builder_destroy(b);
   return bad;
 }
@@ -192,8 +333,13 @@ int main() {
   qg.preds[1] = {0, 0, YBG_PRED_IN_RANGE, 0, (const uint8_t*)ranges,
                  sizeof(ranges)};
 
-  const uint64_t sizes[] = {1,   63,  64,  65,  127, 128, 129,
-                            255, 256, 257, 511, 513, 1025};
+  const uint64_t tile = ybg_sim_snapshot_select_tile_rows();
+  std::vector<uint64_t> sizes = {1,   63,  64,  65,  127, 128, 129,
+                                 255, 256, 257, 511, 513, 1025};
+  // the select's tile width (sizes already in the table are not repeated)
+  for (uint64_t n : {tile - 1, tile, tile + 1, 2 * tile + 1})
+    if (std::find(sizes.begin(), sizes.end(), n) == sizes.end())
+      sizes.push_back(n);
   int bad = 0;
   for (uint64_t n : sizes) {
     bad |= check_one(schema, n, 1000000, q, true);
