@@ -56,6 +56,11 @@ def _lib():
     lib.yb_gpu_scan_close.argtypes = [C.c_void_p]
     lib.yb_gpu_scan_staged.restype = C.c_int
     lib.yb_gpu_scan_staged.argtypes = [C.c_void_p]
+    # absent from a library built before the column plan (YBG_SO may load
+    # one for a before/after measurement)
+    if hasattr(lib, "yb_gpu_scan_planned"):
+        lib.yb_gpu_scan_planned.restype = C.c_int
+        lib.yb_gpu_scan_planned.argtypes = [C.c_void_p]
     lib.yb_gpu_snapshot_build.restype = C.c_int
     lib.yb_gpu_snapshot_build.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.yb_gpu_snapshot_info.restype = C.c_int
@@ -222,6 +227,11 @@ class GpuScan:
         """True when the last execute was answered from a columnar snapshot
         (YBG_STAGE=1 transparent mode)."""
         return bool(self._lib.yb_gpu_scan_staged(self._h))
+
+    def planned(self):
+        """True when the last execute launched the planned fast kernel (the
+        query compiled into a column plan; YBG_PLAN=0 turns it off)."""
+        return bool(self._lib.yb_gpu_scan_planned(self._h))
 
     def snapshot(self):
         """Build a columnar snapshot of the fed tablet at this handle's read

@@ -360,6 +360,13 @@ int yb_gpu_scan_close(ybg_scan_t *s);
  * block-bytes path. */
 int yb_gpu_scan_staged(ybg_scan_t *s);
 
+/* Returns 1 if the last yb_gpu_scan_execute on this handle launched the
+ * planned fast kernel (the query compiled into a column plan: range
+ * predicates on 8-byte integer columns, SUM_INT64 / COUNT / COUNT(*)), 0 if
+ * it ran the interpreted fast kernel, the general kernel or a snapshot.
+ * YBG_PLAN=0 forces 0. Results are identical either way. */
+int yb_gpu_scan_planned(ybg_scan_t *s);
+
 /* ---- columnar snapshot ---------------------------------------------------
  *
  * A DIFFERENT STORAGE CONTRACT from the rest of this header: everything

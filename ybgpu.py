@@ -776,6 +776,28 @@ def sim_scan_fast(spec, data, offsets, n_blocks):
     return res, nf.value
 
 
+def sim_scan_planned(spec):
+    """True when sim_scan_fast runs this spec through the planned
+    packed-row pass (column plan built and YBG_PLAN not 0) — the
+    simulator's yb_gpu_scan_planned. TEST INFRASTRUCTURE."""
+    f = _sig(product(), "ybg_sim_scan_planned", C.c_int,
+             [C.POINTER(ScanSpec)])
+    return bool(f(C.byref(spec)))
+
+
+def sim_plan_extract(buf, value_off, ncols, nc_cap):
+    """The planned pass's column extraction over a packed row of ncols
+    int64 columns whose value starts at buf[value_off] — TEST ONLY.
+    buf: ctypes c_uint8 array. Returns the ncols raw u64 values."""
+    f = _sig(product(), "ybg_sim_plan_extract", C.c_int,
+             [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)])
+    out = (C.c_uint64 * 8)()
+    rc = f(C.addressof(buf) + value_off, ncols, nc_cap, out)
+    if rc != 0:
+        raise RuntimeError(f"ybg_sim_plan_extract failed rc={rc}")
+    return list(out[:ncols])
+
+
 def sim_emit(spec, data, offsets, n_blocks, row_cap=1 << 20,
              varlen_cap=1 << 24):
     """Host-simulator row emission (exact device emit path, serial) —

@@ -4,6 +4,7 @@
 // on CPU. Reference citations are in scan_gpu.hip's header comment.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/yb_gpu_scan.h"
@@ -274,10 +275,35 @@ constexpr uint8_t kGroupEnd = 0x21, kHybridTimeByte = 0x23, kNullLow = 0x24,
 // Byte-level device helpers
 // ---------------------------------------------------------------------------
 
+// Stream pointer into the block DATA buffer (or any other device-global
+// allocation): on device an address_space(1) pointer, so loads through it
+// are global_load (vmcnt only) instead of flat_load (vmcnt AND lgkmcnt —
+// every LDS or scalar-memory wait would also drain the in-flight HBM
+// loads). A pointer that went through uintptr_t arithmetic has lost its
+// address space; this puts it back. Never pass an LDS pointer. In the host
+// simulator it is a plain pointer.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class T>
+using GPtr = const __attribute__((address_space(1))) T*;
+template <class T>
+DEV GPtr<T> gptr(const void* p) {
+  return (GPtr<T>)p;
+}
+#else
+template <class T>
+using GPtr = const T*;
+template <class T>
+DEV GPtr<T> gptr(const void* p) {
+  return (const T*)p;
+}
+#endif
+
 // Unaligned little-endian u64 via three aligned dword loads + funnel shift.
 // The compiler emits per-byte loads for unaligned memcpy on amdgcn; this is
 // 3 loads instead of 8. May read up to 11 bytes past p — every data buffer
 // (generator output, device copy) carries >= 16 bytes of tail slack.
+// load_u64_una takes any pointer (LDS key slots included); load_u64_una_g
+// is the same over device-global memory only (block data, aux).
 DEV uint64_t load_u64_una(const uint8_t* p) {
   uintptr_t a = (uintptr_t)p;
   const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
@@ -286,21 +312,45 @@ DEV uint64_t load_u64_una(const uint8_t* p) {
   if (sh == 0) return lo;
   return (lo >> sh) | ((uint64_t)q[2] << (64 - sh));
 }
+DEV uint64_t load_u64_una_g(const uint8_t* p) {
+  uintptr_t a = (uintptr_t)p;
+  GPtr<uint32_t> q = gptr<uint32_t>((const void*)(a & ~(uintptr_t)3));
+  uint32_t sh = (uint32_t)(a & 3) * 8;
+  uint64_t lo = ((uint64_t)q[1] << 32) | q[0];
+  if (sh == 0) return lo;
+  return (lo >> sh) | ((uint64_t)q[2] << (64 - sh));
+}
+// One unaligned 8-byte load of device-global memory, reading exactly
+// [p, p+8): gfx950 global loads take any byte address, so this is a single
+// global_load_dwordx2 with no shift work and no overread.
+DEV uint64_t load_u64_direct_g(const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef uint64_t __attribute__((aligned(1))) u64_a1;
+  return *(const __attribute__((address_space(1))) u64_a1*)p;
+#else
+  uint64_t u;
+  memcpy(&u, p, 8);
+  return u;
+#endif
+}
 DEV uint64_t load_be64(const uint8_t* p) {
   return __builtin_bswap64(load_u64_una(p));
 }
 DEV uint32_t load_be32(const uint8_t* p) {
   return __builtin_bswap32((uint32_t)load_u64_una(p));
 }
-DEV uint64_t load_le64_u(const uint8_t* p) { return load_u64_una(p); }
-DEV uint32_t load_le32_u(const uint8_t* p) { return (uint32_t)load_u64_una(p); }
+// little-endian fields of the block data (restart arrays, packed-row bodies)
+DEV uint64_t load_le64_u(const uint8_t* p) { return load_u64_una_g(p); }
+DEV uint32_t load_le32_u(const uint8_t* p) {
+  return (uint32_t)load_u64_una_g(p);
+}
 
 // LEB128 varint (rocksdb util/coding.h) — one windowed load covers the
 // 1-4 byte encodings that dominate (block headers); longer forms fall back.
 DEV const uint8_t* leb128(const uint8_t* p, const uint8_t* limit,
                           uint64_t* v) {
   if (p >= limit) return nullptr;
-  uint64_t w = load_u64_una(p);
+  uint64_t w = load_u64_una_g(p);
   uint64_t b0 = w & 0xff;
   if (!(b0 & 0x80)) {
     *v = b0;
@@ -506,7 +556,7 @@ struct Rdr {
   DEV void init(const uint8_t* p) {
     base = (const uint8_t*)((uintptr_t)p & ~(uintptr_t)7);
     k = (uint32_t)((uintptr_t)p & 7);
-    const uint64_t* q = (const uint64_t*)base;
+    GPtr<uint64_t> q = gptr<uint64_t>(base);
     q0 = q[0];
     q1 = q[1];
     q2 = q[2];
@@ -536,7 +586,7 @@ struct Rdr {
       q1 = q2;
       q2 = q3;
       base += 8;
-      q3 = ((const uint64_t*)base)[3];
+      q3 = gptr<uint64_t>(base)[3];
       k -= 8;
     }
   }
@@ -564,7 +614,7 @@ struct Rdr {
       q0 = q2;
       q1 = q3;
       base += 16;
-      const uint64_t* q = (const uint64_t*)base;
+      GPtr<uint64_t> q = gptr<uint64_t>(base);
       q2 = q[2];
       q3 = q[3];
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -771,16 +821,16 @@ DEV const uint8_t* decode_entry_ptr(int fmt, const uint8_t* p,
         bool ch = false;
         uint32_t full = rkb & ~7u;
         for (uint32_t i = 0; i < full; i += 8)
-          if (load_u64_una(&key[i]) != load_u64_una(p + i)) ch = true;
+          if (load_u64_una(&key[i]) != load_u64_una_g(p + i)) ch = true;
         if (rkb & 7) {
           uint64_t m = (1ull << (8 * (rkb & 7))) - 1;
-          if (((load_u64_una(&key[full]) ^ load_u64_una(p + full)) & m) != 0)
+          if (((load_u64_una(&key[full]) ^ load_u64_una_g(p + full)) & m) != 0)
             ch = true;
         }
         if (ch) *changed = true;
       }
       for (uint32_t i = 0; i < ns1; i += 8) {
-        uint64_t w8 = load_u64_una(p + i);
+        uint64_t w8 = load_u64_una_g(p + i);
         __builtin_memcpy(&key[i], &w8, 8);
       }
     } else {
@@ -1838,7 +1888,7 @@ DEV void decode_packed_v2_fixed(const DevSpec& sp, const uint8_t* aux,
   // column i's eval, so the (uniform-trip) loop hides each L1 latency
   // behind the previous column's eval work instead of serializing on it
   const uintptr_t a = (uintptr_t)value;
-  const uint64_t* qw = (const uint64_t*)(a & ~(uintptr_t)7);
+  GPtr<uint64_t> qw = gptr<uint64_t>((const void*)(a & ~(uintptr_t)7));
   const uint32_t abase = (uint32_t)(a & 7);
   const int n = sp.num_value_cols;
   uint32_t ob = abase + sp.v2_off[0];
@@ -1888,7 +1938,7 @@ DEV bool decode_packed_v2_mixed(const DevSpec& sp, const uint8_t* aux,
   const int nfp = sp.v2_nfp, n = sp.num_value_cols;
   if (YBG_UNLIKELY(value + sp.v2_tail_off > end)) return false;
   const uintptr_t a = (uintptr_t)value;
-  const uint64_t* qw = (const uint64_t*)(a & ~(uintptr_t)7);
+  GPtr<uint64_t> qw = gptr<uint64_t>((const void*)(a & ~(uintptr_t)7));
   const uint32_t abase = (uint32_t)(a & 7);
   uint32_t ob = abase + sp.v2_off[0];
   uint64_t w0 = qw[ob >> 3], w1 = qw[(ob >> 3) + 1];
@@ -1925,7 +1975,8 @@ DEV bool decode_packed_v2_mixed(const DevSpec& sp, const uint8_t* aux,
     const uint32_t act = sp.col_act[i];
     const uint32_t fw = (act >> kActV2Shift) & kActV2M;
     uint64_t u;
-    memcpy(&u, p, 8);  // unaligned; block tail slack covers the overread
+    // unaligned; block tail slack covers the overread
+    u = load_u64_direct_g(p);
     if (fw) {
       if (YBG_UNLIKELY(p + fw > end)) return false;
       switch (fw) {
@@ -2552,6 +2603,151 @@ inline bool fast_eligible(const DevSpec& d) {
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// Column plan: the query compiled once per execute into what the fast
+// kernel's packed-row pass needs, so that pass stops interpreting the spec
+// per row (predicate loop over c_spec records, dtype and operator ladders,
+// width switch, aggregate-operator switch). Delivered BY VALUE as a kernel
+// argument: its constants arrive through the kernarg segment.
+//
+// Only LIVE columns appear: a column with no predicate and no aggregate is
+// neither loaded nor looked at. The live columns are kept as two lists so
+// that the kernel carries no per-column role flags (as uniform selects
+// those became lane masks the compiler parked in VGPR lanes, a v_readlane
+// pair per use):
+//   ranged columns  — offset + one inclusive signed range [lo, hi], the
+//                     fold of every predicate on that column. An
+//                     unsatisfiable set is lo = INT64_MAX, hi = INT64_MIN,
+//                     which the same two compares reject for every value.
+//   operand columns — per aggregate slot, the offset of the column it sums.
+// A column that is both is loaded once per list (the second load hits the
+// line the first one fetched).
+// ---------------------------------------------------------------------------
+constexpr int kPlanMaxCols = 8;  // fast_eligible's column cap
+constexpr int kPlanAggs = 2;     // the fast kernel's aggregate slots
+
+struct FastPlan {
+  // ranged column k < n_rng; slots [n_rng, 8) are padding that always
+  // passes (full range, offset 0) so a kernel compiled for more ranged
+  // columns than the query has needs no guard
+  int64_t lo[kPlanMaxCols], hi[kPlanMaxCols];
+  uint8_t off[kPlanMaxCols];      // byte offset from the value start
+  uint32_t n_rng;
+  // aggregate slot g (all zero for g >= num_aggs): val += (operand &
+  // agg_mask) + agg_one, cnt += agg_on
+  uint32_t agg_off[kPlanAggs];    // operand's byte offset (0 = none: the
+                                  // load is masked out)
+  uint32_t agg_mask[kPlanAggs];   // ~0u SUM_INT64, 0 COUNT / COUNT(*)
+  uint32_t agg_one[kPlanAggs];    // 1 COUNT / COUNT(*), 0 SUM_INT64
+  uint32_t agg_on[kPlanAggs];     // 1 when the slot is in use
+  // the per-entry spec fields of the fast shape, so the hot loop reads no
+  // constant memory at all
+  uint32_t rkb, v2_fixed_len, track_restart;
+  HtLim reg_lim;
+};
+
+// Host-side: compile the spec into a plan. false = the spec keeps the
+// interpreted fast kernel (or is not fast_eligible at all). Covered:
+// GT/GE/LT/LE/EQ on 8-byte integer columns, SUM_INT64 over any 8-byte
+// column, COUNT and COUNT(*). Narrower columns may sit in the row as long
+// as no predicate and no SUM touches them (offsets are static).
+inline bool build_fast_plan(const DevSpec& d, FastPlan* pl) {
+  memset(pl, 0, sizeof(*pl));
+  for (int k = 0; k < kPlanMaxCols; ++k) {
+    pl->lo[k] = INT64_MIN;
+    pl->hi[k] = INT64_MAX;
+  }
+  if (!fast_eligible(d) || d.num_aggs > kPlanAggs) return false;
+  auto wide = [&](int c) {
+    return c >= 0 && c < d.num_value_cols && d.cols[c].v2_fixed == 8;
+  };
+  int rng_of[YBG_MAX_COLS];
+  for (int c = 0; c < YBG_MAX_COLS; ++c) rng_of[c] = -1;
+  for (int i = 0; i < d.num_preds; ++i) {
+    const DevPred& pr = d.preds[i];
+    if (pr.op < YBG_PRED_GT || pr.op > YBG_PRED_EQ) return false;  // NE
+    if (!wide(pr.col)) return false;
+    const int dt = d.cols[pr.col].dtype;
+    if (dt != YBG_T_INT64 && dt != YBG_T_UINT64) return false;
+    if (rng_of[pr.col] < 0) {
+      rng_of[pr.col] = (int)pl->n_rng;
+      pl->off[pl->n_rng++] = d.v2_off[pr.col];
+    }
+    const int k = rng_of[pr.col];
+    const int64_t c = (int64_t)pr.datum;
+    int64_t lo = INT64_MIN, hi = INT64_MAX;
+    bool empty = false;
+    switch (pr.op) {
+      case YBG_PRED_GT:
+        if (c == INT64_MAX) empty = true; else lo = c + 1;
+        break;
+      case YBG_PRED_GE: lo = c; break;
+      case YBG_PRED_LT:
+        if (c == INT64_MIN) empty = true; else hi = c - 1;
+        break;
+      case YBG_PRED_LE: hi = c; break;
+      default: lo = hi = c; break;  // EQ
+    }
+    if (lo > pl->lo[k]) pl->lo[k] = lo;
+    if (hi < pl->hi[k]) pl->hi[k] = hi;
+    if (empty || pl->lo[k] > pl->hi[k]) {
+      pl->lo[k] = INT64_MAX;
+      pl->hi[k] = INT64_MIN;
+    }
+  }
+  for (int g = 0; g < d.num_aggs; ++g) {
+    const int op = d.aggs[g].op;
+    pl->agg_on[g] = 1;
+    if (op == YBG_AGG_COUNT_STAR) {
+      pl->agg_one[g] = 1;
+    } else if (op == YBG_AGG_COUNT) {
+      // COUNT's operand is never NULL in the fast shape (rows with a null
+      // mask abort the batch), so it counts every matched row — but only
+      // a column that exists clears the slot's null bit on the
+      // interpreted path, so the column must be a real one
+      if (d.aggs[g].col < 0 || d.aggs[g].col >= d.num_value_cols)
+        return false;
+      pl->agg_one[g] = 1;
+    } else if (op == YBG_AGG_SUM_INT64) {
+      if (!wide(d.aggs[g].col)) return false;
+      pl->agg_off[g] = d.v2_off[d.aggs[g].col];
+      pl->agg_mask[g] = ~0u;
+    } else {
+      return false;  // MIN / MAX / SUM_DOUBLE are not additive on u64
+    }
+  }
+  pl->rkb = d.fixed_rk_len;
+  pl->v2_fixed_len = d.v2_fixed_len;
+  pl->track_restart = (uint32_t)d.track_restart;
+  pl->reg_lim = d.reg_lim;
+  return true;
+}
+
+// The planned kernel's compile-time ranged-column count for a plan: exact
+// up to 4, then 8 (padding slots always pass).
+inline int fast_plan_nr(const FastPlan& pl) {
+  return pl.n_rng <= 4 ? (int)pl.n_rng : kPlanMaxCols;
+}
+
+// YBG_PLAN=0 keeps a plannable spec on the interpreted fast kernel (the
+// GPU dispatch and the simulator read the same knob).
+inline bool fast_plan_enabled() {
+  const char* e = getenv("YBG_PLAN");
+  return !e || atoi(e) != 0;
+}
+
+// Load pass of the planned packed-row pass: N columns' 8 bytes at the
+// given offsets from the value start, one direct global load each, issued
+// back to back — no alignment work, no shared-word shuffling, no branch,
+// no wait in between. A real column reads exactly [value + off, value +
+// off + 8); a padding slot reads the 8 bytes at the value start, inside
+// the buffer's tail slack even for the shortest row.
+template <int N, class OffT>
+DEV void plan_load_cols(const OffT* off, const uint8_t* value, uint64_t* uv) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) uv[k] = load_u64_direct_g(value + off[k]);
+}
+
 #ifndef YBG_FABORT
 #define YBG_FABORT(n) return 0
 #endif
@@ -2572,7 +2768,13 @@ inline bool fast_eligible(const DevSpec& d) {
 // with unconditional LDS writes (best on MVCC version chains, where the
 // below-rkb bound makes lane trip counts diverge and every byte would
 // otherwise be extracted twice). Results are identical.
-template <int NA, int NC, bool FUSE = false>
+// PLAN runs the packed-row pass and the row-boundary accumulate from the
+// compiled column plan *pl (build_fast_plan) instead of interpreting sp;
+// everything else — entry decode, visibility, row splitting, head/walk and
+// the abort protocol — is the same code. pl is only read when PLAN, and
+// NC is then the number of RANGED columns the pass evaluates
+// (fast_plan_nr: 0..4 or 8), not the schema's column cap.
+template <int NA, int NC, bool FUSE = false, bool PLAN = false>
 DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
                         const uint64_t* block_offsets, const Interval* ivs,
                         uint64_t n_ivs, uint64_t j_lo, uint64_t j_hi,
@@ -2580,7 +2782,10 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
                         uint32_t* entries, uint32_t* scanned,
                         uint32_t* matched, uint64_t* agg_val,
                         uint64_t* agg_cnt, HeadOut<NA>* ho,
-                        bool* walked_next_out) {
+                        bool* walked_next_out,
+                        const FastPlan* pl = nullptr) {
+  static_assert(!PLAN || (NA == kPlanAggs && NC <= kPlanMaxCols),
+                "plan shape");
   Interval iv = ivs[j_lo];
   const uint8_t* blk = data + block_offsets[iv.block];
   const uint8_t* p = blk + iv.start;
@@ -2606,11 +2811,47 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
   bool row_open = false, in_head = true, walked = false;
   bool base_seen = false, found = false;
   uint32_t pred_pass = 0, agg_null = 0xffffffffu;
+  bool row_pass = true;  // PLAN: every ranged column so far is in range
   uint64_t agg_datum[NA];
 #pragma unroll
   for (int g = 0; g < NA; ++g) agg_datum[g] = 0;
-  const uint32_t rkb = sp.fixed_rk_len;
+  const uint32_t rkb = PLAN ? pl->rkb : sp.fixed_rk_len;
+  const HtLim& reg_lim = PLAN ? pl->reg_lim : sp.reg_lim;
   EntryRef er;
+  // one finalized row into (scanned, matched, val, cnt) — the head record
+  // or the batch-local accumulators
+  auto acc_row = [&](uint32_t* sc, uint32_t* mt, uint64_t* val,
+                     uint64_t* cnt) {
+    *sc += 1;
+    if constexpr (PLAN) {
+      if (row_pass) {
+        *mt += 1;
+#pragma unroll
+        for (int g = 0; g < NA; ++g) {
+          // additive slots only: SUM_INT64 adds its operand, the counting
+          // forms add one (their operand load is masked out)
+          const uint32_t m = pl->agg_mask[g];
+          const uint64_t d = ((uint64_t)((uint32_t)(agg_datum[g] >> 32) & m)
+                              << 32) |
+                             ((uint32_t)agg_datum[g] & m);
+          val[g] += d + pl->agg_one[g];
+          cnt[g] += pl->agg_on[g];
+        }
+      }
+    } else {
+      if ((pred_pass & sp.value_pred_mask) == sp.value_pred_mask) {
+        *mt += 1;
+#pragma unroll
+        for (int g = 0; g < NA; ++g) {
+          if (g >= sp.num_aggs) continue;
+          bool nul = (sp.agg_op[g] != YBG_AGG_COUNT_STAR) &&
+                     ((agg_null >> g) & 1);
+          if (!nul)
+            combine_datum(sp.agg_op[g], &val[g], &cnt[g], agg_datum[g]);
+        }
+      }
+    }
+  };
 
   for (;;) {
     if (p >= limit) {
@@ -2637,7 +2878,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // tail needs ukey >= 16) abort to the general path.
       at_restart = false;
       if (limit - p < 3) YBG_FABORT(1);
-      uint64_t w = load_u64_una(p);
+      uint64_t w = load_u64_una_g(p);
       uint32_t b0 = (uint32_t)(w & 0xff);
       uint64_t e1;
       uint32_t e1len;
@@ -2666,19 +2907,22 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       if (row_open) {
         uint32_t full = rkb & ~7u;
         for (uint32_t i = 0; i < full; i += 8)
-          if (load_u64_una(&key[i]) != load_u64_una(kp2 + i)) kchg = true;
+          if (load_u64_una(&key[i]) != load_u64_una_g(kp2 + i)) kchg = true;
         if (rkb & 7) {
           uint64_t m = (1ull << (8 * (rkb & 7))) - 1;
-          if (((load_u64_una(&key[full]) ^ load_u64_una(kp2 + full)) & m))
+          if (((load_u64_una(&key[full]) ^ load_u64_una_g(kp2 + full)) & m))
             kchg = true;
         }
       }
       for (uint32_t i = 0; i < ns1; i += 8) {
-        uint64_t w8 = load_u64_una(kp2 + i);
+        uint64_t w8 = load_u64_una_g(kp2 + i);
         __builtin_memcpy(&key[i], &w8, 8);
       }
       key_len = ns1;
-      tail_from_lds(kp2, ns1 - 8, &thi, &tlo);
+      // the key bytes still sit in the block data: tail_from_lds's two
+      // loads, over global memory
+      thi = __builtin_bswap64(load_u64_una_g(kp2 + ns1 - 24));
+      tlo = __builtin_bswap64(load_u64_una_g(kp2 + ns1 - 16));
       er.value = kp2 + ns1;
       er.value_len = value_size;
       er.shared = 0;
@@ -2851,37 +3095,8 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
     if (kchg) {
       if (row_open) {
         if (found) {
-          bool hit = (pred_pass & sp.value_pred_mask) == sp.value_pred_mask;
-          if (in_head) {
-            ho->scanned += 1;
-            if (hit) {
-              ho->matched += 1;
-#pragma unroll
-              for (int g = 0; g < NA; ++g) {
-                if (g >= sp.num_aggs) continue;
-                bool nul = (sp.agg_op[g] != YBG_AGG_COUNT_STAR) &&
-                           ((agg_null >> g) & 1);
-                if (!nul) {
-                  combine_datum(sp.agg_op[g], &ho->val[g], &ho->cnt[g],
-                                agg_datum[g]);
-                }
-              }
-            }
-          } else {
-            s_b += 1;
-            if (hit) {
-              m_b += 1;
-#pragma unroll
-              for (int g = 0; g < NA; ++g) {
-                if (g >= sp.num_aggs) continue;
-                bool nul = (sp.agg_op[g] != YBG_AGG_COUNT_STAR) &&
-                           ((agg_null >> g) & 1);
-                if (!nul)
-                  combine_datum(sp.agg_op[g], &av_b[g], &ac_b[g],
-                                agg_datum[g]);
-              }
-            }
-          }
+          if (in_head) acc_row(&ho->scanned, &ho->matched, ho->val, ho->cnt);
+          else acc_row(&s_b, &m_b, av_b, ac_b);
         }
         in_head = false;
         row_open = false;
@@ -2892,6 +3107,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       found = false;
       pred_pass = 0;
       agg_null = 0xffffffffu;
+      row_pass = true;
     }
     e_b += (cur_iv < j_hi);
     walked |= (cur_iv == j_hi);
@@ -2900,10 +3116,10 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         er.value_len ? (uint32_t)(rdr.peek8() & 0xff) : 0u;
     if (YBG_UNLIKELY(vb0 == kHybridTimeByte)) YBG_FABORT(23);
     const bool visible =
-        u128_slice_cmp(ht_hi, ht_lo, ht_sz, sp.reg_lim.hi, sp.reg_lim.lo,
-                       sp.reg_lim.len) >= 0;
+        u128_slice_cmp(ht_hi, ht_lo, ht_sz, reg_lim.hi, reg_lim.lo,
+                       reg_lim.len) >= 0;
     if (visible) {
-      if (YBG_UNLIKELY(sp.track_restart)) {
+      if (YBG_UNLIKELY(PLAN ? pl->track_restart : sp.track_restart)) {
         if (u128_slice_cmp(ht_hi, ht_lo, ht_sz, sp.read.hi, sp.read.lo,
                            sp.read.len) < 0) {
           uint64_t* rr = rmin;
@@ -2917,61 +3133,78 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       }
       if (!base_seen) {
         base_seen = true;
-        if (YBG_LIKELY(er.value_len == sp.v2_fixed_len && vb0 == kPackedV2B &&
+        if (YBG_LIKELY(er.value_len ==
+                           (PLAN ? pl->v2_fixed_len : sp.v2_fixed_len) &&
+                       vb0 == kPackedV2B &&
                        (rdr.peek8() & 0xff8000u) == 0)) {
           const uint8_t* value = rdr.pos();
           rdr.seek(value + er.value_len);  // next window loads issue now
-          // fixed-offset column extraction (decode_packed_v2_fixed, lean
-          // eval) in two fully-unrolled passes: a branch-free load pass
-          // issuing all NC word pairs, then the eval pass over registers
-          // (see the NC doc on scan_batch_fast)
-          const uintptr_t a = (uintptr_t)value;
-          const uint64_t* qw = (const uint64_t*)(a & ~(uintptr_t)7);
-          const uint32_t abase = (uint32_t)(a & 7);
-          uint64_t uv[NC];
+          if constexpr (PLAN) {
+            // planned pass: every live-column load, then two compares
+            // per ranged column — no predicate loop, no dtype / operator /
+            // width dispatch, no branch
+            uint64_t uv[NC > 0 ? NC : 1];
+            plan_load_cols<NC>(pl->off, value, uv);
+            plan_load_cols<NA>(pl->agg_off, value, agg_datum);
 #pragma unroll
-          for (int i = 0; i < NC; ++i) {
-            const uint32_t ob = abase + sp.v2_off[i];
-            const uint32_t wi = ob >> 3, shb = (ob & 7) * 8;
-            const uint64_t w0 = qw[wi], w1 = qw[wi + 1];
-            uv[i] = shb ? (w0 >> shb) | (w1 << (64 - shb)) : w0;
-          }
-#pragma unroll
-          for (int i = 0; i < NC; ++i) {
-            const uint32_t act = sp.col_act[i];
-            uint64_t u = uv[i];
-            const uint32_t dt = (act >> kActDtShift) & kActDtM;
-            switch ((act >> kActV2Shift) & kActV2M) {
-              case 1:
-                u = (dt == YBG_T_INT8) ? (uint64_t)(int64_t)(int8_t)u
-                                       : (u & 0xff);
-                break;
-              case 2:
-                u = (dt == YBG_T_INT16) ? (uint64_t)(int64_t)(int16_t)u
-                                        : (u & 0xffff);
-                break;
-              case 4:
-                u = (dt == YBG_T_INT32) ? (uint64_t)(int64_t)(int32_t)u
-                                        : (u & 0xffffffffull);
-                break;
-              default:
-                break;
+            for (int k = 0; k < NC; ++k) {
+              const int64_t v = (int64_t)uv[k];
+              row_pass &= (v >= pl->lo[k]) & (v <= pl->hi[k]);
             }
-            uint32_t pm = act & kActPredM;
-            while (pm) {
-              int pi = __builtin_ctz(pm);
-              pm &= pm - 1;
-              bool pass = pred_cmp_fast(sp.predc[pi], u);
-              pred_pass =
-                  (pred_pass & ~(1u << pi)) | ((uint32_t)pass << pi);
-            }
-            uint32_t am = (act >> kActAggShift) & kActAggM;
-            if (am) {
+          } else {
+            // fixed-offset column extraction (decode_packed_v2_fixed, lean
+            // eval) in two fully-unrolled passes: a branch-free load pass
+            // issuing all NC word pairs, then the eval pass over registers
+            // (see the NC doc on scan_batch_fast)
+            const uintptr_t a = (uintptr_t)value;
+            GPtr<uint64_t> qw =
+                gptr<uint64_t>((const void*)(a & ~(uintptr_t)7));
+            const uint32_t abase = (uint32_t)(a & 7);
+            uint64_t uv[NC];
 #pragma unroll
-              for (int g = 0; g < NA; ++g) {
-                if (am & (1u << g)) {
-                  agg_datum[g] = u;
-                  agg_null &= ~(1u << g);
+            for (int i = 0; i < NC; ++i) {
+              const uint32_t ob = abase + sp.v2_off[i];
+              const uint32_t wi = ob >> 3, shb = (ob & 7) * 8;
+              const uint64_t w0 = qw[wi], w1 = qw[wi + 1];
+              uv[i] = shb ? (w0 >> shb) | (w1 << (64 - shb)) : w0;
+            }
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+              const uint32_t act = sp.col_act[i];
+              uint64_t u = uv[i];
+              const uint32_t dt = (act >> kActDtShift) & kActDtM;
+              switch ((act >> kActV2Shift) & kActV2M) {
+                case 1:
+                  u = (dt == YBG_T_INT8) ? (uint64_t)(int64_t)(int8_t)u
+                                         : (u & 0xff);
+                  break;
+                case 2:
+                  u = (dt == YBG_T_INT16) ? (uint64_t)(int64_t)(int16_t)u
+                                          : (u & 0xffff);
+                  break;
+                case 4:
+                  u = (dt == YBG_T_INT32) ? (uint64_t)(int64_t)(int32_t)u
+                                          : (u & 0xffffffffull);
+                  break;
+                default:
+                  break;
+              }
+              uint32_t pm = act & kActPredM;
+              while (pm) {
+                int pi = __builtin_ctz(pm);
+                pm &= pm - 1;
+                bool pass = pred_cmp_fast(sp.predc[pi], u);
+                pred_pass =
+                    (pred_pass & ~(1u << pi)) | ((uint32_t)pass << pi);
+              }
+              uint32_t am = (act >> kActAggShift) & kActAggM;
+              if (am) {
+#pragma unroll
+                for (int g = 0; g < NA; ++g) {
+                  if (am & (1u << g)) {
+                    agg_datum[g] = u;
+                    agg_null &= ~(1u << g);
+                  }
                 }
               }
             }
@@ -2991,35 +3224,8 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
   }
   // final open row
   if (row_open && found) {
-    bool hit = (pred_pass & sp.value_pred_mask) == sp.value_pred_mask;
-    if (in_head) {
-      ho->scanned += 1;
-      if (hit) {
-        ho->matched += 1;
-#pragma unroll
-        for (int g = 0; g < NA; ++g) {
-          if (g >= sp.num_aggs) continue;
-          bool nul = (sp.agg_op[g] != YBG_AGG_COUNT_STAR) &&
-                     ((agg_null >> g) & 1);
-          if (!nul)
-            combine_datum(sp.agg_op[g], &ho->val[g], &ho->cnt[g],
-                          agg_datum[g]);
-        }
-      }
-    } else {
-      s_b += 1;
-      if (hit) {
-        m_b += 1;
-#pragma unroll
-        for (int g = 0; g < NA; ++g) {
-          if (g >= sp.num_aggs) continue;
-          bool nul = (sp.agg_op[g] != YBG_AGG_COUNT_STAR) &&
-                     ((agg_null >> g) & 1);
-          if (!nul)
-            combine_datum(sp.agg_op[g], &av_b[g], &ac_b[g], agg_datum[g]);
-        }
-      }
-    }
+    if (in_head) acc_row(&ho->scanned, &ho->matched, ho->val, ho->cnt);
+    else acc_row(&s_b, &m_b, av_b, ac_b);
   }
   *entries += e_b;
   *scanned += s_b;

@@ -39,6 +39,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "scan_device.h"
@@ -225,7 +226,14 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
 // same global bheads/walked protocol.
 // ---------------------------------------------------------------------------
 
-template <int WPS, int NC, bool FUSE = false>
+// PLAN: the packed-row pass runs from a compiled column plan that arrives
+// by value in the kernarg segment (scan_device.h FastPlan); the
+// interpreted kernel takes an empty struct in its place.
+struct NoPlan {};
+template <bool PLAN>
+using PlanArg = std::conditional_t<PLAN, FastPlan, NoPlan>;
+
+template <int WPS, int NC, bool FUSE = false, bool PLAN = false>
 __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
     const uint8_t* __restrict__ data,
     const uint64_t* __restrict__ block_offsets,
@@ -234,8 +242,10 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
     uint8_t* __restrict__ walked, uint64_t ivb, uint64_t n_bat,
     const uint64_t* __restrict__ batch_lo,
     uint64_t* __restrict__ retry_ids,
-    unsigned long long* __restrict__ retry_n) {
+    unsigned long long* __restrict__ retry_n, const PlanArg<PLAN> plan) {
   const DevSpec& sp = c_spec;
+  const FastPlan* pl = nullptr;
+  if constexpr (PLAN) pl = &plan;
   __shared__ uint8_t key_scratch[kThreads * kFastKeyCap];
   __shared__ uint64_t rmin_scratch[kThreads * 3];
   uint8_t* key = key_scratch + (size_t)threadIdx.x * kFastKeyCap;
@@ -256,10 +266,9 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
     bool walked_next = false;
     uint64_t lo, hi;
     batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
-    if (!scan_batch_fast<NA, NC, FUSE>(sp, data, block_offsets, ivs, n_ivs,
-                                       lo, hi,
-                             key, rmin, &entries, &scanned, &matched,
-                             agg_val, agg_cnt, &ho, &walked_next)) {
+    if (!scan_batch_fast<NA, NC, FUSE, PLAN>(
+            sp, data, block_offsets, ivs, n_ivs, lo, hi, key, rmin, &entries,
+            &scanned, &matched, agg_val, agg_cnt, &ho, &walked_next, pl)) {
       unsigned long long slot = atomicAdd(retry_n, 1ull);
       retry_ids[slot] = j;
       continue;
@@ -898,6 +907,7 @@ struct ybg_scan {
   ybg_snapshot_t* stage_snap = nullptr;
   bool stage_failed = false;  // the build failed once: stay on the block path
   bool staged_last = false;   // last execute was answered from the snapshot
+  bool planned_last = false;  // last execute launched the planned fast kernel
 };
 
 extern "C" {
@@ -1678,6 +1688,7 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
   // aggregates is answered from a columnar snapshot built on the first
   // execute. Anything else — and a failed build — takes the block path.
   s->staged_last = false;
+  s->planned_last = false;
   {
     const char* e = getenv("YBG_STAGE");
     if (e && atoi(e) == 1 && !s->stage_failed && !s->spec.emit_rows &&
@@ -1724,11 +1735,11 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
   if (usefast) {
     HIP_TRY(hipMemsetAsync(s->d_retry_n, 0, sizeof(unsigned long long),
                            s->stream));
-    auto launchf = [&](auto kern) {
+    auto launchf = [&](auto kern, auto plan) {
       hipLaunchKernelGGL(kern, dim3(s->grid), dim3(kThreads), 0, s->stream,
                          s->d_data, s->d_offsets, s->d_ivs, s->n_ivs,
                          s->d_partials, s->d_heads, s->d_walked, s->ivb,
-                         n_bat, bat_lo, s->d_retry, s->d_retry_n);
+                         n_bat, bat_lo, s->d_retry, s->d_retry_n, plan);
     };
     // NC: compile-time column cap for the unrolled load pass (spec is
     // zero-padded up to it; fast_eligible caps num_value_cols at 8).
@@ -1737,12 +1748,31 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
     const bool nc4 = s->dspec.num_value_cols <= 4;
     bool fuse = s->dspec.fuse_hint != 0;
     if (const char* e = getenv("YBG_FUSE")) fuse = atoi(e) != 0;
-    if (fuse) {
-      if (nc4) launchf(k_scan_fast<3, 4, true>);
-      else launchf(k_scan_fast<3, 8, true>);
+    // a plannable query runs the planned kernel: its packed-row pass is
+    // compiled from the spec here, once, instead of interpreted per row
+    FastPlan plan;
+    s->planned_last = build_fast_plan(s->dspec, &plan) && fast_plan_enabled();
+    if (s->planned_last) {
+      // compiled per ranged-column count, so the pass has no guards
+      auto launchp = [&](auto nr_tag) {
+        constexpr int NR = decltype(nr_tag)::value;
+        if (fuse) launchf(k_scan_fast<3, NR, true, true>, plan);
+        else launchf(k_scan_fast<3, NR, false, true>, plan);
+      };
+      switch (fast_plan_nr(plan)) {
+        case 0: launchp(std::integral_constant<int, 0>{}); break;
+        case 1: launchp(std::integral_constant<int, 1>{}); break;
+        case 2: launchp(std::integral_constant<int, 2>{}); break;
+        case 3: launchp(std::integral_constant<int, 3>{}); break;
+        case 4: launchp(std::integral_constant<int, 4>{}); break;
+        default: launchp(std::integral_constant<int, 8>{}); break;
+      }
+    } else if (fuse) {
+      if (nc4) launchf(k_scan_fast<3, 4, true>, NoPlan{});
+      else launchf(k_scan_fast<3, 8, true>, NoPlan{});
     } else {
-      if (nc4) launchf(k_scan_fast<3, 4>);
-      else launchf(k_scan_fast<3, 8>);
+      if (nc4) launchf(k_scan_fast<3, 4>, NoPlan{});
+      else launchf(k_scan_fast<3, 8>, NoPlan{});
     }
     // retry pass: the general kernel over the aborted batch list, into
     // the second partials half
@@ -2076,6 +2106,8 @@ int yb_gpu_scan_kernel_ms(ybg_scan_t* s, double* total_ms, double* decode_ms) {
 }
 
 int yb_gpu_scan_staged(ybg_scan_t* s) { return s->staged_last ? 1 : 0; }
+
+int yb_gpu_scan_planned(ybg_scan_t* s) { return s->planned_last ? 1 : 0; }
 
 int yb_gpu_scan_close(ybg_scan_t* s) {
   if (s->stage_snap) yb_gpu_snapshot_close(s->stage_snap);

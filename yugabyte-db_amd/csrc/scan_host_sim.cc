@@ -169,27 +169,46 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
   alignas(8) uint8_t key[kKeyCap];
   alignas(8) uint8_t rk_save[kKeyCap];
   uint64_t bht[6] = {0, 0, 0, 0, 0, 0};
+  // the GPU dispatch's choice: a plannable spec runs the planned pass
+  FastPlan plan;
+  const bool planned = build_fast_plan(d, &plan) && fast_plan_enabled();
   for (uint64_t b = 0; b < n_b; ++b) {
     bool wn = false;
     uint32_t e32 = 0, s32 = 0, m32 = 0;
     uint64_t lo = b * ivb;
     uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
-    // NC and FUSE mirror the GPU dispatch so CPU fuzz covers both
-    // compiled shapes of the fast decode
-    auto call_fast = [&](auto fuse_tag) {
-      constexpr bool F = decltype(fuse_tag)::value;
-      return d.num_value_cols <= 4
-                 ? scan_batch_fast<2, 4, F>(d, data, offsets, ivs.data(),
-                                            n_ivs, lo, hi, key, bht + 3,
-                                            &e32, &s32, &m32, agg_val,
-                                            agg_cnt, &heads[b], &wn)
-                 : scan_batch_fast<2, 8, F>(d, data, offsets, ivs.data(),
-                                            n_ivs, lo, hi, key, bht + 3,
-                                            &e32, &s32, &m32, agg_val,
-                                            agg_cnt, &heads[b], &wn);
+    // NC, FUSE and PLAN mirror the GPU dispatch so CPU fuzz covers every
+    // compiled shape of the fast kernel
+    auto call_fast = [&](auto nc_tag, auto plan_tag) {
+      constexpr int N = decltype(nc_tag)::value;
+      constexpr bool P = decltype(plan_tag)::value;
+      auto run = [&](auto fuse_tag) {
+        constexpr bool F = decltype(fuse_tag)::value;
+        return scan_batch_fast<2, N, F, P>(d, data, offsets, ivs.data(),
+                                           n_ivs, lo, hi, key, bht + 3, &e32,
+                                           &s32, &m32, agg_val, agg_cnt,
+                                           &heads[b], &wn, &plan);
+      };
+      return d.fuse_hint ? run(std::true_type{}) : run(std::false_type{});
     };
-    int rc = d.fuse_hint ? call_fast(std::true_type{})
-                         : call_fast(std::false_type{});
+    using std::integral_constant;
+    const std::true_type plan_on{};
+    const std::false_type plan_off{};
+    int rc;
+    if (planned) {
+      switch (fast_plan_nr(plan)) {
+        case 0: rc = call_fast(integral_constant<int, 0>{}, plan_on); break;
+        case 1: rc = call_fast(integral_constant<int, 1>{}, plan_on); break;
+        case 2: rc = call_fast(integral_constant<int, 2>{}, plan_on); break;
+        case 3: rc = call_fast(integral_constant<int, 3>{}, plan_on); break;
+        case 4: rc = call_fast(integral_constant<int, 4>{}, plan_on); break;
+        default: rc = call_fast(integral_constant<int, 8>{}, plan_on); break;
+      }
+    } else if (d.num_value_cols <= 4) {
+      rc = call_fast(integral_constant<int, 4>{}, plan_off);
+    } else {
+      rc = call_fast(integral_constant<int, 8>{}, plan_off);
+    }
     if (!rc) {
       ++fallbacks;
       uint64_t av8[YBG_MAX_AGGS] = {0}, ac8[YBG_MAX_AGGS] = {0};
@@ -223,6 +242,33 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
   }
   store_result(d, entries, scanned, matched, agg_val, agg_cnt, bht, out);
   if (n_fallback_out) *n_fallback_out = fallbacks;
+  return 0;
+}
+
+// 1 when ybg_sim_scan_fast would run this spec through the planned pass
+// (build_fast_plan succeeds and YBG_PLAN does not turn it off), else 0 —
+// the simulator-side yb_gpu_scan_planned.
+int ybg_sim_scan_planned(const ybg_scan_spec_t* spec) {
+  DevSpec d;
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
+  FastPlan plan;
+  return build_fast_plan(d, &plan) && fast_plan_enabled() ? 1 : 0;
+}
+
+// TEST ONLY: the planned pass's column extraction (plan_load_cols) over a
+// packed row of ncols (<= 8) int64 columns starting at `value`, every
+// column listed; out[k] = column k. nc_cap picks the compiled count (4 or
+// 8); slots past ncols are padding and read the value start.
+int ybg_sim_plan_extract(const uint8_t* value, int ncols, int nc_cap,
+                         uint64_t* out) {
+  if (ncols < 1 || ncols > nc_cap || (nc_cap != 4 && nc_cap != 8)) return 1;
+  uint8_t off[8] = {0};  // slots past ncols are padding, as in a plan
+  for (int k = 0; k < ncols; ++k) off[k] = (uint8_t)(3 + 8 * k);
+  uint64_t uv[8] = {0};
+  if (nc_cap == 4) plan_load_cols<4>(off, value, uv);
+  else plan_load_cols<8>(off, value, uv);
+  for (int k = 0; k < ncols; ++k) out[k] = uv[k];
   return 0;
 }
 
