@@ -61,6 +61,10 @@ def _lib():
     if hasattr(lib, "yb_gpu_scan_planned"):
         lib.yb_gpu_scan_planned.restype = C.c_int
         lib.yb_gpu_scan_planned.argtypes = [C.c_void_p]
+    if hasattr(lib, "yb_gpu_scan_retry_batches"):  # same: newer than the plan
+        lib.yb_gpu_scan_retry_batches.restype = C.c_int
+        lib.yb_gpu_scan_retry_batches.argtypes = [C.c_void_p,
+                                                  C.POINTER(C.c_uint64)]
     lib.yb_gpu_snapshot_build.restype = C.c_int
     lib.yb_gpu_snapshot_build.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.yb_gpu_snapshot_info.restype = C.c_int
@@ -232,6 +236,15 @@ class GpuScan:
         """True when the last execute launched the planned fast kernel (the
         query compiled into a column plan; YBG_PLAN=0 turns it off)."""
         return bool(self._lib.yb_gpu_scan_planned(self._h))
+
+    def retry_batches(self):
+        """Batches the last execute handed from the fast kernel to the
+        general kernel (0 when no fast kernel ran). Waits for the execute."""
+        n = C.c_uint64()
+        self._check(
+            self._lib.yb_gpu_scan_retry_batches(self._h, C.byref(n)),
+            "retry_batches")
+        return n.value
 
     def snapshot(self):
         """Build a columnar snapshot of the fed tablet at this handle's read

@@ -367,6 +367,16 @@ int yb_gpu_scan_staged(ybg_scan_t *s);
  * YBG_PLAN=0 forces 0. Results are identical either way. */
 int yb_gpu_scan_planned(ybg_scan_t *s);
 
+/* How many batches the last yb_gpu_scan_execute on this handle handed from
+ * the fast kernel to the general kernel (entry forms outside the fast
+ * shape): the batches of the handle's remembered abort set, launched next to
+ * the fast kernel, plus the ones that aborted late. Waits for the execute.
+ * 0 when the execute did not run a fast kernel (general dispatch, snapshot,
+ * bloom-rejected). Returns 0 or an error code. YBG_KNOWN=0 keeps every
+ * execute on the serial order (fast kernel, then the retry launch); results
+ * are identical either way. */
+int yb_gpu_scan_retry_batches(ybg_scan_t *s, uint64_t *n_out);
+
 /* ---- columnar snapshot ---------------------------------------------------
  *
  * A DIFFERENT STORAGE CONTRACT from the rest of this header: everything

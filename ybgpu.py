@@ -776,6 +776,30 @@ def sim_scan_fast(spec, data, offsets, n_blocks):
     return res, nf.value
 
 
+def sim_scan_fast_known(spec, data, offsets, n_blocks, known_ids):
+    """sim_scan_fast given a known abort set (batch ids, any order): listed
+    batches go straight to the general scanner — TEST INFRASTRUCTURE.
+    Returns (ScanResult, ids of every batch the general scanner ran)."""
+    f = _sig(product(), "ybg_sim_scan_fast_known", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+              C.c_uint64, C.POINTER(ScanResult), C.POINTER(C.c_uint64),
+              C.POINTER(C.c_uint64), C.c_uint64])
+    res = ScanResult()
+    nf = C.c_uint64()
+    known = (C.c_uint64 * max(len(known_ids), 1))(*known_ids)
+    cap = 1 << 16
+    while True:
+        ids = (C.c_uint64 * cap)()
+        rc = f(C.byref(spec), data, offsets, n_blocks, known, len(known_ids),
+               C.byref(res), C.byref(nf), ids, cap)
+        if rc != 0:
+            raise RuntimeError(f"ybg_sim_scan_fast_known failed rc={rc}")
+        if nf.value <= cap:
+            return res, list(ids[:nf.value])
+        cap = nf.value
+
+
 def sim_scan_planned(spec):
     """True when sim_scan_fast runs this spec through the planned
     packed-row pass (column plan built and YBG_PLAN not 0) — the
@@ -783,6 +807,17 @@ def sim_scan_planned(spec):
     f = _sig(product(), "ybg_sim_scan_planned", C.c_int,
              [C.POINTER(ScanSpec)])
     return bool(f(C.byref(spec)))
+
+
+HEAD_NONE, HEAD_FOLD, HEAD_WRITE = 0, 1, 2
+
+
+def sim_head_action(lane, ok, p_ok, p_wn):
+    """The planned fast kernel's per-lane head-row decision (scan_device.h
+    head_action) — TEST ONLY. Returns HEAD_NONE / HEAD_FOLD / HEAD_WRITE."""
+    f = _sig(product(), "ybg_sim_head_action", C.c_int,
+             [C.c_uint, C.c_int, C.c_int, C.c_int])
+    return f(lane, int(ok), int(p_ok), int(p_wn))
 
 
 def sim_plan_extract(buf, value_off, ncols, nc_cap):

@@ -2175,6 +2175,33 @@ struct HeadOut {
   uint32_t scanned, matched;
 };
 
+// Per-batch state byte (d_walked): written by whichever kernel completes the
+// batch, read by the fold (k_fold).
+//   bit 0  the batch's tail walk consumed the next batch's head row
+//   bit 1  the batch's head record is pending in the global head array; the
+//          fold adds it iff the predecessor's bit 0 is clear
+constexpr uint8_t kBatchWalked = 1;
+constexpr uint8_t kBatchHeadPending = 2;
+
+// What a lane of the planned fast kernel does with its batch's deferred
+// head row. Lane l holds batch j and lane l-1 batch j-1 (the grid-stride
+// span is a multiple of the wave size), so when both completed on the fast
+// path the predecessor's answer is one shuffle away:
+//   kHeadFold   the head row is this batch's own: add it to the lane's
+//               accumulators, write no record
+//   kHeadNone   nothing to add or write: the batch aborted / is inactive
+//               (the retry kernel writes its record and state), or the
+//               predecessor's walk consumed the head row
+//   kHeadWrite  the predecessor is in another wave or did not complete
+//               here: write the record, mark it pending
+// ok = this lane's batch completed; p_ok / p_wn = lane l-1's ok / walked.
+enum HeadAction { kHeadNone = 0, kHeadFold = 1, kHeadWrite = 2 };
+DEV HeadAction head_action(unsigned lane, bool ok, bool p_ok, bool p_wn) {
+  if (!ok) return kHeadNone;
+  if (lane > 0 && p_ok) return p_wn ? kHeadNone : kHeadFold;
+  return kHeadWrite;
+}
+
 // ---------------------------------------------------------------------------
 // GROUP BY partial aggregates (config #5). Open-addressing hash table in
 // device memory: state[] 0=empty / 2=claiming / 1=ready, gkey[] the group

@@ -26,8 +26,8 @@
 //    its head row was already consumed by the predecessor's walk; only
 //    intervals at workgroup boundaries (1 in 256) write a global head record
 //    + continuation flag, folded by the final reduction.
-//  * The final single-workgroup reduction folds wave partials and boundary
-//    head records IN FIXED ORDER => results (including double SUM) are
+//  * The fold (k_fold; k_reduce on the grouped scan) combines wave partials
+//    and head records IN FIXED ORDER => results (including double SUM) are
 //    deterministic run-to-run.
 //
 // The per-interval algorithm itself lives in scan_device.h and is also
@@ -145,10 +145,12 @@ __device__ __forceinline__ void wave_fold_partials(
 // ---------------------------------------------------------------------------
 
 // Head resolution is GLOBAL: every batch writes its deferred head record
-// (compact 2*NA+2 u64 stride) and its walked flag; k_reduce_pre folds
-// head records whose predecessor batch did not walk into them. No
-// relay, no syncthreads, and batches may be processed by ANY kernel in
-// any launch (the fast kernel + its retry pass rely on this).
+// (compact 2*NA+2 u64 stride) and its state byte (scan_device.h
+// kBatchWalked | kBatchHeadPending); k_fold adds the pending head records
+// whose predecessor batch did not walk into them. No relay, no
+// syncthreads, and batches may be processed by ANY kernel in any launch
+// (the fast kernel + its retry pass rely on this). The planned fast kernel
+// resolves most heads inside the wave and leaves only the rest pending.
 // retry_ids/retry_n, when set, make the kernel process only the listed
 // batches (the fast kernel's aborts).
 template <int NA, int WPS>
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
     }
     hr[2 * NA] = ho.scanned;
     hr[2 * NA + 1] = ho.matched;
-    walked[j] = walked_next ? 1 : 0;
+    walked[j] = kBatchHeadPending | (walked_next ? kBatchWalked : 0);
   }
 
   __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
@@ -225,6 +227,15 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan(
 // retry list and re-run by k_scan in retry mode; head resolution is the
 // same global bheads/walked protocol.
 // ---------------------------------------------------------------------------
+
+// known_bits, when set, is the handle's remembered abort set (one bit per
+// batch): a listed batch is skipped at once, the general kernel is already
+// running it from the known list (see "Known abort set" in the host code).
+// A wave's 64 batches share one word.
+__device__ __forceinline__ bool batch_known(
+    const uint64_t* __restrict__ known_bits, uint64_t j) {
+  return known_bits && ((known_bits[j >> 6] >> (j & 63)) & 1);
+}
 
 // PLAN: the packed-row pass runs from a compiled column plan that arrives
 // by value in the kernarg segment (scan_device.h FastPlan); the
@@ -242,7 +253,8 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
     uint8_t* __restrict__ walked, uint64_t ivb, uint64_t n_bat,
     const uint64_t* __restrict__ batch_lo,
     uint64_t* __restrict__ retry_ids,
-    unsigned long long* __restrict__ retry_n, const PlanArg<PLAN> plan) {
+    unsigned long long* __restrict__ retry_n,
+    const uint64_t* __restrict__ known_bits, const PlanArg<PLAN> plan) {
   const DevSpec& sp = c_spec;
   const FastPlan* pl = nullptr;
   if constexpr (PLAN) pl = &plan;
@@ -261,27 +273,82 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
 #pragma unroll
   for (int g = 0; g < NA; ++g) { agg_val[g] = 0; agg_cnt[g] = 0; }
 
-  for (uint64_t j = gtid; j < n_bat; j += span) {
-    HeadOut<NA> ho;
-    bool walked_next = false;
-    uint64_t lo, hi;
-    batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
-    if (!scan_batch_fast<NA, NC, FUSE, PLAN>(
+  if constexpr (PLAN) {
+    // Heads resolved inside the wave. span is a multiple of the wave size,
+    // so lane l holds batch j and lane l-1 batch j-1 in every pass: the
+    // loop is wave-uniform (an active flag, no early exit) so the shuffles
+    // run converged. Every plan slot is an additive wrapping int64
+    // (SUM_INT64, COUNT, COUNT(*)), so adding a head row here instead of in
+    // the fold cannot change a bit of the result. Only heads whose
+    // predecessor is in another wave or did not complete here go through
+    // the global record.
+    const unsigned lane = threadIdx.x & 63;
+    for (uint64_t j0 = 0; j0 < n_bat; j0 += span) {
+      const uint64_t j = j0 + gtid;
+      HeadOut<NA> ho;
+      bool walked_next = false;
+      bool ok = false;
+      if (j < n_bat && !batch_known(known_bits, j)) {
+        uint64_t lo, hi;
+        batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
+        ok = scan_batch_fast<NA, NC, FUSE, PLAN>(
             sp, data, block_offsets, ivs, n_ivs, lo, hi, key, rmin, &entries,
-            &scanned, &matched, agg_val, agg_cnt, &ho, &walked_next, pl)) {
-      unsigned long long slot = atomicAdd(retry_n, 1ull);
-      retry_ids[slot] = j;
-      continue;
-    }
-    uint64_t* hr = bheads + j * kHS;
+            &scanned, &matched, agg_val, agg_cnt, &ho, &walked_next, pl);
+        if (!ok) {
+          unsigned long long slot = atomicAdd(retry_n, 1ull);
+          retry_ids[slot] = j;
+        }
+      }
+      const int wn = (ok && walked_next) ? 1 : 0;
+      const int p_ok = __shfl_up(ok ? 1 : 0, 1);
+      const int p_wn = __shfl_up(wn, 1);
+      const HeadAction act = head_action(lane, ok, p_ok != 0, p_wn != 0);
+      if (act == kHeadFold) {
+        scanned += ho.scanned;
+        matched += ho.matched;
 #pragma unroll
-    for (int g = 0; g < NA; ++g) {
-      hr[2 * g] = ho.val[g];
-      hr[2 * g + 1] = ho.cnt[g];
+        for (int g = 0; g < NA; ++g) {
+          agg_val[g] += ho.val[g];
+          agg_cnt[g] += ho.cnt[g];
+        }
+      } else if (act == kHeadWrite) {
+        uint64_t* hr = bheads + j * kHS;
+#pragma unroll
+        for (int g = 0; g < NA; ++g) {
+          hr[2 * g] = ho.val[g];
+          hr[2 * g + 1] = ho.cnt[g];
+        }
+        hr[2 * NA] = ho.scanned;
+        hr[2 * NA + 1] = ho.matched;
+      }
+      if (ok)
+        walked[j] = (uint8_t)(wn | (act == kHeadWrite ? kBatchHeadPending : 0));
     }
-    hr[2 * NA] = ho.scanned;
-    hr[2 * NA + 1] = ho.matched;
-    walked[j] = walked_next ? 1 : 0;
+  } else {
+    for (uint64_t j = gtid; j < n_bat; j += span) {
+      if (batch_known(known_bits, j)) continue;
+      HeadOut<NA> ho;
+      bool walked_next = false;
+      uint64_t lo, hi;
+      batch_bounds(batch_lo, j, ivb, n_ivs, &lo, &hi);
+      if (!scan_batch_fast<NA, NC, FUSE, PLAN>(
+              sp, data, block_offsets, ivs, n_ivs, lo, hi, key, rmin,
+              &entries, &scanned, &matched, agg_val, agg_cnt, &ho,
+              &walked_next, pl)) {
+        unsigned long long slot = atomicAdd(retry_n, 1ull);
+        retry_ids[slot] = j;
+        continue;
+      }
+      uint64_t* hr = bheads + j * kHS;
+#pragma unroll
+      for (int g = 0; g < NA; ++g) {
+        hr[2 * g] = ho.val[g];
+        hr[2 * g + 1] = ho.cnt[g];
+      }
+      hr[2 * NA] = ho.scanned;
+      hr[2 * NA + 1] = ho.matched;
+      walked[j] = kBatchHeadPending | (walked_next ? kBatchWalked : 0);
+    }
   }
 
   // errs = 0: the fast scanner aborts a batch instead of failing it
@@ -522,105 +589,210 @@ struct DevResult {
   uint64_t restart_hi, restart_lo, restart_len;
 };
 
-// Pre-reduction: workgroup c folds a CONTIGUOUS chunk of wave partials and
-// head records (fixed thread-strided order inside the chunk) into one
-// partial-layout record; k_reduce then folds the 256 chunk records in fixed
-// order. The fold tree is fixed => results stay deterministic run-to-run;
-// the single-workgroup k_reduce no longer reads megabytes through one CU.
-// hstride = the bheads per-batch record stride (2 * dispatch-NA + 2);
-// a batch's head record folds in iff its predecessor did not walk into it.
-__global__ __launch_bounds__(256) void k_reduce_pre(
-    DevSpec sp, const uint64_t* __restrict__ partials, uint64_t n_partials,
-    const uint64_t* __restrict__ bheads, const uint8_t* __restrict__ walked,
-    uint64_t n_batches, int hstride, uint64_t* __restrict__ chunk_out) {
-  __shared__ uint64_t sval[256], scnt[256], scal[256];
-  const unsigned t = threadIdx.x;
-  const uint64_t nch = gridDim.x;
-  const uint64_t pl = (n_partials + nch - 1) / nch;
-  const uint64_t plo = blockIdx.x * pl;
-  const uint64_t phi = plo + pl < n_partials ? plo + pl : n_partials;
-  const uint64_t hl = (n_batches + nch - 1) / nch;
-  const uint64_t hlo = blockIdx.x * hl;
-  const uint64_t hhi = hlo + hl < n_batches ? hlo + hl : n_batches;
+// Fold kernel: ONE launch turns the wave partial records, the batch state
+// bytes and the pending head records into DevResult.
+//  * Workgroup c owns a contiguous range of partial records and a
+//    contiguous range of batches. A thread reads its records whole, in
+//    index order (only the aggregate slots in use; the restart triple only
+//    under track_restart), then its batches' state bytes four at a time (a
+//    wave reads 256 contiguous bytes) and loads d_heads[j] only where the
+//    head is pending and the predecessor did not walk into it.
+//  * Threads combine in fixed lane order (shuffles), waves in fixed wave
+//    order (LDS), and the workgroup writes one chunk record.
+//  * The workgroup then takes a ticket; the one drawing the last ticket
+//    folds the chunk records IN INDEX ORDER (never arrival order) into
+//    DevResult and sets the ticket counter back to 0. No workgroup waits
+//    for another.
+// The fold tree is a fixed function of the grid and the batch count, so
+// results (double SUM included) are bit-identical run to run.
+// hstride = the bheads per-batch record stride (2 * dispatch-NA + 2).
+constexpr int kFoldGrid = 512;
+constexpr int kFoldThreads = 256;
 
-  for (int s = 0; s < 4; ++s) {
-    uint64_t acc = 0;
-    for (uint64_t i = plo + t; i < phi; i += 256)
-      acc += partials[i * kPartialStride + s];
-    if (s == 1 || s == 2) {
-      for (uint64_t i = hlo + t; i < hhi; i += 256)
-        if (i == 0 || walked[i - 1] == 0)
-          acc += bheads[i * hstride + hstride - 2 + (s - 1)];
-    }
-    scal[t] = acc;
-    __syncthreads();
-    if (t == 0) {
-      uint64_t total = 0;
-      for (int i = 0; i < 256; ++i) total += scal[i];
-      chunk_out[blockIdx.x * kPartialStride + s] = total;
-    }
-    __syncthreads();
-  }
-  for (int g = 0; g < sp.num_aggs; ++g) {
-    int op = sp.agg_op[g];
-    uint64_t av = 0, ac = 0;
-    for (uint64_t i = plo + t; i < phi; i += 256)
-      combine1(op, &av, &ac, partials[i * kPartialStride + 4 + 2 * g],
-               partials[i * kPartialStride + 4 + 2 * g + 1]);
-    for (uint64_t i = hlo + t; i < hhi; i += 256) {
-      if (i > 0 && walked[i - 1] != 0) continue;
-      combine1(op, &av, &ac, bheads[i * hstride + 2 * g],
-               bheads[i * hstride + 2 * g + 1]);
-    }
-    sval[t] = av;
-    scnt[t] = ac;
-    __syncthreads();
-    if (t == 0) {
-      uint64_t fv = 0, fc = 0;
-      for (int i = 0; i < 256; ++i) combine1(op, &fv, &fc, sval[i], scnt[i]);
-      chunk_out[blockIdx.x * kPartialStride + 4 + 2 * g] = fv;
-      chunk_out[blockIdx.x * kPartialStride + 4 + 2 * g + 1] = fc;
-    }
-    __syncthreads();
-  }
-  {
-    // restart-min fold (encoded-HT MIN; len 0 = none)
-    const int rb = 4 + 2 * YBG_MAX_AGGS;
-    uint64_t mh = 0, ml = 0, mn = 0;
-    for (uint64_t i = plo + t; i < phi; i += 256) {
-      uint64_t n = partials[i * kPartialStride + rb + 2];
-      if (n == 0) continue;
-      uint64_t h = partials[i * kPartialStride + rb];
-      uint64_t l = partials[i * kPartialStride + rb + 1];
-      if (mn == 0 ||
-          u128_slice_cmp(h, l, (uint32_t)n, mh, ml, (uint32_t)mn) < 0) {
-        mh = h;
-        ml = l;
-        mn = n;
-      }
-    }
-    sval[t] = mh;
-    scnt[t] = ml;
-    scal[t] = mn;
-    __syncthreads();
-    if (t == 0) {
-      uint64_t fh = 0, fl = 0, fn = 0;
-      for (int i = 0; i < 256; ++i) {
-        if (scal[i] == 0) continue;
-        if (fn == 0 || u128_slice_cmp(sval[i], scnt[i], (uint32_t)scal[i],
-                                      fh, fl, (uint32_t)fn) < 0) {
-          fh = sval[i];
-          fl = scnt[i];
-          fn = scal[i];
-        }
-      }
-      chunk_out[blockIdx.x * kPartialStride + rb] = fh;
-      chunk_out[blockIdx.x * kPartialStride + rb + 1] = fl;
-      chunk_out[blockIdx.x * kPartialStride + rb + 2] = fn;
-    }
+struct FoldAcc {
+  uint64_t cnt[4];  // entries, scanned, matched, errs
+  uint64_t av[YBG_MAX_AGGS], ac[YBG_MAX_AGGS];
+  uint64_t rh, rl, rn;  // restart minimum (rn == 0: none)
+};
+
+__device__ __forceinline__ void fold_restart(FoldAcc* a, uint64_t h,
+                                             uint64_t l, uint64_t n) {
+  if (n == 0) return;
+  if (a->rn == 0 || u128_slice_cmp(h, l, (uint32_t)n, a->rh, a->rl,
+                                   (uint32_t)a->rn) < 0) {
+    a->rh = h;
+    a->rl = l;
+    a->rn = n;
   }
 }
 
+// one partial-layout record into the accumulator
+__device__ __forceinline__ void fold_record(const DevSpec& sp, bool restart,
+                                            FoldAcc* a, const uint64_t* r) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) a->cnt[s] += r[s];
+#pragma unroll
+  for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+    if (g >= sp.num_aggs) continue;
+    combine1(sp.agg_op[g], &a->av[g], &a->ac[g], r[4 + 2 * g],
+             r[4 + 2 * g + 1]);
+  }
+  if (restart) {
+    const int rb = 4 + 2 * YBG_MAX_AGGS;
+    fold_restart(a, r[rb], r[rb + 1], r[rb + 2]);
+  }
+}
+
+__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int off) {
+  return (uint64_t)__shfl_down((unsigned long long)v, off);
+}
+
+// Workgroup reduction of every thread's accumulator into thread 0's:
+// lanes by a fixed shuffle tree, then the waves in wave order through LDS.
+// lds holds (kFoldThreads / 64) * kPartialStride u64.
+__device__ __forceinline__ void fold_workgroup(const DevSpec& sp,
+                                               bool restart, FoldAcc* a,
+                                               uint64_t* lds) {
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a->cnt[s] += shfl_down_u64(a->cnt[s], off);
+#pragma unroll
+    for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+      if (g >= sp.num_aggs) continue;  // workgroup-uniform
+      uint64_t bv = shfl_down_u64(a->av[g], off);
+      uint64_t bc = shfl_down_u64(a->ac[g], off);
+      combine1(sp.agg_op[g], &a->av[g], &a->ac[g], bv, bc);
+    }
+    if (restart) {
+      uint64_t h = shfl_down_u64(a->rh, off);
+      uint64_t l = shfl_down_u64(a->rl, off);
+      uint64_t n = shfl_down_u64(a->rn, off);
+      fold_restart(a, h, l, n);
+    }
+  }
+  if (lane == 0) {
+    uint64_t* w = lds + wave * kPartialStride;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) w[s] = a->cnt[s];
+#pragma unroll
+    for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+      w[4 + 2 * g] = a->av[g];
+      w[4 + 2 * g + 1] = a->ac[g];
+    }
+    w[4 + 2 * YBG_MAX_AGGS] = a->rh;
+    w[4 + 2 * YBG_MAX_AGGS + 1] = a->rl;
+    w[4 + 2 * YBG_MAX_AGGS + 2] = a->rn;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int v = 1; v < kFoldThreads / 64; ++v)
+      fold_record(sp, restart, a, lds + v * kPartialStride);
+  }
+}
+
+__global__ __launch_bounds__(kFoldThreads) void k_fold(
+    DevSpec sp, const uint64_t* __restrict__ partials, uint64_t n_partials,
+    const uint64_t* __restrict__ bheads, const uint8_t* __restrict__ state,
+    uint64_t n_batches, int hstride, uint64_t* chunk, unsigned* ticket,
+    DevResult* __restrict__ out) {
+  __shared__ uint64_t lds[(kFoldThreads / 64) * kPartialStride];
+  __shared__ unsigned s_ticket;
+  const unsigned t = threadIdx.x;
+  const uint64_t nch = gridDim.x;
+  const bool restart = sp.track_restart != 0;
+  FoldAcc a;
+  memset(&a, 0, sizeof(a));
+
+  // partial records [plo, phi)
+  const uint64_t pl = (n_partials + nch - 1) / nch;
+  const uint64_t plo = blockIdx.x * pl;
+  const uint64_t phi = plo + pl < n_partials ? plo + pl : n_partials;
+  for (uint64_t i = plo + t; i < phi; i += kFoldThreads)
+    fold_record(sp, restart, &a, partials + i * kPartialStride);
+
+  // batches [hlo, hhi), hlo a multiple of 4: a thread takes 4 consecutive
+  // state bytes in one aligned load (the array is padded to a multiple of
+  // 4 bytes) plus the byte before them
+  const uint64_t hl = (((n_batches + nch - 1) / nch) + 3) & ~3ull;
+  const uint64_t hlo = blockIdx.x * hl;
+  const uint64_t hhi = hlo + hl < n_batches ? hlo + hl : n_batches;
+  for (uint64_t j4 = hlo + 4ull * t; j4 < hhi; j4 += 4ull * kFoldThreads) {
+    uint32_t st4;
+    __builtin_memcpy(&st4, state + j4, 4);
+    uint32_t prev = j4 > 0 ? state[j4 - 1] : 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint64_t j = j4 + b;
+      const uint32_t st = (st4 >> (8 * b)) & 0xff;
+      if (j < hhi && (st & kBatchHeadPending) && !(prev & kBatchWalked)) {
+        const uint64_t* hr = bheads + j * hstride;
+        a.cnt[1] += hr[hstride - 2];
+        a.cnt[2] += hr[hstride - 1];
+#pragma unroll
+        for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+          if (g >= sp.num_aggs) continue;
+          combine1(sp.agg_op[g], &a.av[g], &a.ac[g], hr[2 * g],
+                   hr[2 * g + 1]);
+        }
+      }
+      prev = st;
+    }
+  }
+
+  fold_workgroup(sp, restart, &a, lds);
+  uint64_t* mine = chunk + (uint64_t)blockIdx.x * kPartialStride;
+  if (t == 0) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) mine[s] = a.cnt[s];
+#pragma unroll
+    for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+      mine[4 + 2 * g] = a.av[g];
+      mine[4 + 2 * g + 1] = a.ac[g];
+    }
+    mine[4 + 2 * YBG_MAX_AGGS] = a.rh;
+    mine[4 + 2 * YBG_MAX_AGGS + 1] = a.rl;
+    mine[4 + 2 * YBG_MAX_AGGS + 2] = a.rn;
+    __threadfence();  // the record is visible before the ticket is taken
+    s_ticket = atomicAdd(ticket, 1u);
+  }
+  __syncthreads();
+  if (s_ticket != nch - 1) return;  // workgroup-uniform
+
+  // last workgroup: every chunk record is written and fenced. Thread t
+  // folds records t, t + 256, ... in index order; the reads bypass the
+  // non-coherent cache path (agent-scope atomic loads).
+  __threadfence();
+  memset(&a, 0, sizeof(a));
+  for (uint64_t i = t; i < nch; i += kFoldThreads) {
+    uint64_t r[kPartialStride];
+#pragma unroll
+    for (int k = 0; k < kPartialStride; ++k)
+      r[k] = ybg_atomic_load_u64(
+          (unsigned long long*)(chunk + i * kPartialStride + k));
+    fold_record(sp, restart, &a, r);
+  }
+  __syncthreads();  // lds is reused
+  fold_workgroup(sp, restart, &a, lds);
+  if (t == 0) {
+    out->entries = a.cnt[0];
+    out->scanned = a.cnt[1];
+    out->matched = a.cnt[2];
+    out->errs = a.cnt[3];
+    for (int g = 0; g < YBG_MAX_AGGS; ++g) {
+      out->agg_val[g] = a.av[g];
+      out->agg_cnt[g] = a.ac[g];
+    }
+    out->restart_hi = a.rh;
+    out->restart_lo = a.rl;
+    out->restart_len = a.rn;
+    *ticket = 0;  // every workgroup has drawn: ready for the next launch
+  }
+}
+
+// Single-workgroup reduction of the grouped scan's partial records and
+// workgroup-boundary head records (cont_flags protocol).
 __global__ __launch_bounds__(256) void k_reduce(
     DevSpec sp, const uint64_t* __restrict__ partials, uint64_t n_partials,
     const uint64_t* __restrict__ heads, const uint32_t* __restrict__ cont_flags,
@@ -850,10 +1022,11 @@ struct ybg_scan {
   uint64_t total_bytes = 0;
   uint8_t* d_aux = nullptr;
   uint8_t* d_rk_save = nullptr;
-  uint64_t* d_partials = nullptr;  // 2 halves: main launch + retry launch
+  uint64_t* d_partials = nullptr;  // 3 regions: main | retry/known | late
   uint64_t n_partials = 0;
   uint64_t* d_heads = nullptr;   // per-batch head records (stride hstride)
-  uint8_t* d_walked = nullptr;   // per-batch walked-into-next flag
+  uint8_t* d_walked = nullptr;   // per-batch state byte (kBatchWalked |
+                                 // kBatchHeadPending)
   uint64_t* d_retry = nullptr;   // fast-kernel aborted batch ids
   unsigned long long* d_retry_n = nullptr;
   uint32_t* d_cont = nullptr;    // k_group relay flags (per 256 batches)
@@ -862,7 +1035,38 @@ struct ybg_scan {
   int na_cap = 2;
   int hstride = 6;
   DevResult* d_result = nullptr;
-  uint64_t* d_chunk = nullptr;  // k_reduce_pre output (256 partial records)
+  uint64_t* d_chunk = nullptr;  // k_fold chunk records (kFoldGrid)
+  unsigned* d_fold_ticket = nullptr;  // k_fold arrival counter, 0 at rest
+  uint64_t last_retry_batches = 0;  // batches the last execute handed to
+                                    // the general kernel (known + late)
+  unsigned long long* h_retry_n = nullptr;  // pinned: d_retry_n of the last
+                                            // fast execute, copied after it
+  bool retry_pending = false;  // ...not yet looked at by wait
+  // Known abort set (see yb_gpu_scan_execute): the batches the fast kernel
+  // aborted in an earlier execute of this handle, as a sorted id list and a
+  // bitmap, valid for one batch decomposition and kernel variant
+  hipStream_t stream2 = nullptr;  // runs the known-list launch
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  struct KnownKey {
+    uint64_t n_bat = 0, ivb = 0;
+    bool bb = false;
+    int variant = -1;
+    bool operator==(const KnownKey& o) const {
+      return n_bat == o.n_bat && ivb == o.ivb && bb == o.bb &&
+             variant == o.variant;
+    }
+  };
+  bool known_valid = false;
+  KnownKey known_key;
+  std::vector<uint64_t> known_ids;  // sorted ascending
+  uint64_t* d_known = nullptr;      // known_ids on the device
+  unsigned long long* d_known_n = nullptr;
+  uint64_t* d_known_bits = nullptr;  // one bit per batch
+  // the last fast execute: its key, how many known batches it launched,
+  // and whether wait may learn from it (YBG_KNOWN)
+  KnownKey last_key;
+  uint64_t last_known_n = 0;
+  bool last_learn = false;
   int grid = 0;
   bool executed = false;
   // bloom filter proved the scan's pinned key prefix absent at feed
@@ -1008,7 +1212,12 @@ int yb_gpu_scan_open(const ybg_scan_spec_t* spec, ybg_scan_t** out) {
   if ((e = hipStreamCreate(&s->stream)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_start)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_mid)) != hipSuccess ||
-      (e = hipEventCreate(&s->ev_end)) != hipSuccess) {
+      (e = hipEventCreate(&s->ev_end)) != hipSuccess ||
+      (e = hipStreamCreate(&s->stream2)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming)) !=
+          hipSuccess ||
+      (e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming)) !=
+          hipSuccess) {
     delete s;
     return set_err(10, hipGetErrorString(e));
   }
@@ -1397,20 +1606,26 @@ int yb_gpu_scan_feed_blocks(ybg_scan_t* s, const uint8_t* blocks,
   s->na_cap = s->dspec.num_aggs <= 2 ? 2 : (s->dspec.num_aggs <= 4 ? 4 : 8);
   s->hstride = 2 * s->na_cap + 2;
   HIP_TRY(hipMalloc(&s->d_rk_save, span_threads * kKeyCap));
+  // three regions: main launch | retry or known-list launch | late launch
   HIP_TRY(hipMalloc(&s->d_partials,
-                    2 * s->n_partials * kPartialStride * sizeof(uint64_t)));
+                    3 * s->n_partials * kPartialStride * sizeof(uint64_t)));
   HIP_TRY(hipMalloc(&s->d_heads,
                     s->n_heads * s->hstride * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc(&s->d_walked, s->n_heads ? s->n_heads : 1));
+  // + 8: k_fold reads the state bytes four at a time
+  HIP_TRY(hipMalloc(&s->d_walked, s->n_heads + 8));
   HIP_TRY(hipMalloc(&s->d_retry,
                     (s->n_heads ? s->n_heads : 1) * sizeof(uint64_t)));
   HIP_TRY(hipMalloc(&s->d_retry_n, sizeof(unsigned long long)));
+  HIP_TRY(hipHostMalloc(&s->h_retry_n, sizeof(unsigned long long)));
+  s->known_valid = false;  // a feed drops the known abort set
   HIP_TRY(hipMalloc(&s->d_cont,
                     ((s->n_batches + kThreads - 1) / kThreads) *
                         sizeof(uint32_t)));
   HIP_TRY(hipMalloc(&s->d_result, sizeof(DevResult)));
   HIP_TRY(hipMalloc(&s->d_chunk,
-                    1024 * kPartialStride * sizeof(uint64_t)));
+                    kFoldGrid * kPartialStride * sizeof(uint64_t)));
+  HIP_TRY(hipMalloc(&s->d_fold_ticket, sizeof(unsigned)));
+  HIP_TRY(hipMemset(s->d_fold_ticket, 0, sizeof(unsigned)));
   return 0;
 }
 
@@ -1618,11 +1833,10 @@ int scan_flags_stats(ybg_scan_t* s, const DevSpec& d, ScanStats* out) {
   rsp.num_aggs = 0;
   DevResult* d_res = nullptr;
   HIP_TRY(hipMalloc(&d_res, sizeof(DevResult)));
-  hipLaunchKernelGGL(k_reduce_pre, dim3(1024), dim3(256), 0, s->stream, rsp,
-                     s->d_partials, s->n_partials, s->d_heads, s->d_walked,
-                     s->n_batches, 6, s->d_chunk);
-  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, s->stream, rsp,
-                     s->d_chunk, 1024, s->d_heads, s->d_cont, 0, d_res);
+  hipLaunchKernelGGL(k_fold, dim3(kFoldGrid), dim3(kFoldThreads), 0,
+                     s->stream, rsp, s->d_partials, s->n_partials, s->d_heads,
+                     s->d_walked, s->n_batches, 6, s->d_chunk,
+                     s->d_fold_ticket, d_res);
   DevResult r;
   hipError_t e = hipMemcpyAsync(&r, d_res, sizeof(r), hipMemcpyDeviceToHost,
                                 s->stream);
@@ -1676,6 +1890,52 @@ int scan_emit_pass(ybg_scan_t* s, const uint8_t* d_aux, EmitCtx ec,
 
 }  // namespace ybgint
 
+namespace {
+
+// After a fast execute has finished: merge the batches it aborted (n_late
+// ids in d_retry) into the handle's known abort set and upload list and
+// bitmap. Runs once per change of the set — the list is a few hundred KB at
+// most on the headline tablet.
+int known_learn(ybg_scan_t* s, uint64_t n_late) {
+  if (!s->known_valid || !(s->known_key == s->last_key)) {
+    s->known_ids.clear();
+    s->known_key = s->last_key;
+    s->known_valid = false;
+  }
+  if (n_late > s->n_heads) return set_err(10, "retry list overran");
+  if (n_late) {
+    const size_t old = s->known_ids.size();
+    s->known_ids.resize(old + n_late);
+    HIP_TRY(hipMemcpy(s->known_ids.data() + old, s->d_retry,
+                      n_late * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::sort(s->known_ids.begin(), s->known_ids.end());
+    s->known_ids.erase(
+        std::unique(s->known_ids.begin(), s->known_ids.end()),
+        s->known_ids.end());
+    const uint64_t words = s->n_heads / 64 + 1;
+    if (!s->d_known) {
+      HIP_TRY(hipMalloc(&s->d_known, s->n_heads * sizeof(uint64_t)));
+      HIP_TRY(hipMalloc(&s->d_known_n, sizeof(unsigned long long)));
+      HIP_TRY(hipMalloc(&s->d_known_bits, words * sizeof(uint64_t)));
+    }
+    std::vector<uint64_t> bits(words, 0);
+    for (uint64_t j : s->known_ids) {
+      if (j >= s->n_heads) return set_err(10, "retry list holds a bad id");
+      bits[j >> 6] |= 1ull << (j & 63);
+    }
+    const unsigned long long n = s->known_ids.size();
+    HIP_TRY(hipMemcpy(s->d_known, s->known_ids.data(), n * sizeof(uint64_t),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_known_n, &n, sizeof(n), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_known_bits, bits.data(), words * sizeof(uint64_t),
+                      hipMemcpyHostToDevice));
+  }
+  s->known_valid = true;
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int yb_gpu_scan_execute(ybg_scan_t* s) {
@@ -1689,6 +1949,8 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
   // execute. Anything else — and a failed build — takes the block path.
   s->staged_last = false;
   s->planned_last = false;
+  s->last_retry_batches = 0;
+  s->retry_pending = false;
   {
     const char* e = getenv("YBG_STAGE");
     if (e && atoi(e) == 1 && !s->stage_failed && !s->spec.emit_rows &&
@@ -1710,12 +1972,6 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
       }
     }
   }
-  // the retry half of the partials is only partially covered by the retry
-  // launch (or not at all on the general dispatch): zero it so the fold
-  // sees clean records
-  HIP_TRY(hipMemsetAsync(
-      s->d_partials + s->n_partials * kPartialStride, 0,
-      s->n_partials * kPartialStride * sizeof(uint64_t), s->stream));
   HIP_TRY(hipEventRecord(s->ev_start, s->stream));
   HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_spec), &s->dspec,
                                  sizeof(DevSpec), 0, hipMemcpyHostToDevice,
@@ -1732,15 +1988,13 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
   if (const char* e = getenv("YBG_BB")) use_bb = atoi(e) != 0;
   const uint64_t n_bat = use_bb ? s->n_blocks : s->n_batches;
   const uint64_t* bat_lo = use_bb ? s->d_batch_lo : nullptr;
+  // partial records the fold reads: the main half, plus exactly the
+  // records a retry launch writes (the rest of the retry half is never
+  // initialized)
+  uint64_t n_fold = s->n_partials;
   if (usefast) {
     HIP_TRY(hipMemsetAsync(s->d_retry_n, 0, sizeof(unsigned long long),
                            s->stream));
-    auto launchf = [&](auto kern, auto plan) {
-      hipLaunchKernelGGL(kern, dim3(s->grid), dim3(kThreads), 0, s->stream,
-                         s->d_data, s->d_offsets, s->d_ivs, s->n_ivs,
-                         s->d_partials, s->d_heads, s->d_walked, s->ivb,
-                         n_bat, bat_lo, s->d_retry, s->d_retry_n, plan);
-    };
     // NC: compile-time column cap for the unrolled load pass (spec is
     // zero-padded up to it; fast_eligible caps num_value_cols at 8).
     // fuse: version-chain decode shape per the spec's expect_versions
@@ -1752,6 +2006,64 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
     // compiled from the spec here, once, instead of interpreted per row
     FastPlan plan;
     s->planned_last = build_fast_plan(s->dspec, &plan) && fast_plan_enabled();
+    const int nr = s->planned_last ? fast_plan_nr(plan) : 0;
+
+    // Known abort set. Which batches the fast kernel aborts depends on the
+    // entry encodings in the immutable block bytes and on the batch
+    // decomposition, not on the query, so the list one execute produced is
+    // known before the next one starts: the general kernel then runs it on
+    // a second stream NEXT TO the fast kernel instead of after it, and the
+    // fast kernel skips those batches by bitmap.
+    // INVARIANT: any batch may be run by the general kernel, and a batch
+    // the fast kernel aborts that the set did not predict is still
+    // appended to the late list and run by the late launch below. A stale
+    // or wrong set can therefore cost time and can never change a result.
+    // The set is dropped when its key (batch decomposition, kernel
+    // variant) changes and at feed; YBG_KNOWN=0 keeps every execute on the
+    // serial order.
+    ybg_scan::KnownKey key;
+    key.n_bat = n_bat;
+    key.ivb = s->ivb;
+    key.bb = use_bb;
+    key.variant = (s->planned_last ? 64 : 0) | (fuse ? 32 : 0) |
+                  (s->planned_last ? nr : (nc4 ? 4 : 8));
+    bool learn = true;
+    if (const char* e = getenv("YBG_KNOWN")) learn = atoi(e) != 0;
+    if (s->known_valid && !(s->known_key == key)) s->known_valid = false;
+    const bool use_known = learn && s->known_valid && !s->known_ids.empty();
+    s->last_key = key;
+    s->last_learn = learn;
+    s->last_known_n = use_known ? s->known_ids.size() : 0;
+
+    const int rg = std::min(s->grid, 1024);
+    auto general_kernel = k_scan<2, 3>;
+    // the general kernel over a batch id list, into its own partials region
+    auto launch_list = [&](hipStream_t st, int g, uint64_t* region,
+                           const uint64_t* ids,
+                           const unsigned long long* n_ids) {
+      hipLaunchKernelGGL(general_kernel, dim3(g), dim3(kThreads), 0, st,
+                         s->d_data, s->d_offsets, s->d_ivs, s->n_ivs,
+                         s->d_aux, s->d_rk_save, region, s->d_heads,
+                         s->d_walked, nullptr, 0, s->ivb, n_bat, bat_lo, ids,
+                         n_ids);
+    };
+    uint64_t* region1 = s->d_partials + s->n_partials * kPartialStride;
+    if (use_known) {
+      // fork after the c_spec upload; enqueued before the fast kernel so
+      // its workgroups get placed first
+      HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
+      HIP_TRY(hipStreamWaitEvent(s->stream2, s->ev_fork, 0));
+      launch_list(s->stream2, rg, region1, s->d_known, s->d_known_n);
+      HIP_TRY(hipEventRecord(s->ev_join, s->stream2));
+    }
+    const uint64_t* known_bits = use_known ? s->d_known_bits : nullptr;
+    auto launchf = [&](auto kern, auto plan) {
+      hipLaunchKernelGGL(kern, dim3(s->grid), dim3(kThreads), 0, s->stream,
+                         s->d_data, s->d_offsets, s->d_ivs, s->n_ivs,
+                         s->d_partials, s->d_heads, s->d_walked, s->ivb,
+                         n_bat, bat_lo, s->d_retry, s->d_retry_n, known_bits,
+                         plan);
+    };
     if (s->planned_last) {
       // compiled per ranged-column count, so the pass has no guards
       auto launchp = [&](auto nr_tag) {
@@ -1759,7 +2071,7 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
         if (fuse) launchf(k_scan_fast<3, NR, true, true>, plan);
         else launchf(k_scan_fast<3, NR, false, true>, plan);
       };
-      switch (fast_plan_nr(plan)) {
+      switch (nr) {
         case 0: launchp(std::integral_constant<int, 0>{}); break;
         case 1: launchp(std::integral_constant<int, 1>{}); break;
         case 2: launchp(std::integral_constant<int, 2>{}); break;
@@ -1774,16 +2086,21 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
       if (nc4) launchf(k_scan_fast<3, 4>, NoPlan{});
       else launchf(k_scan_fast<3, 8>, NoPlan{});
     }
-    // retry pass: the general kernel over the aborted batch list, into
-    // the second partials half
-    int rg = std::min(s->grid, 1024);
-    auto retry_kernel = k_scan<2, 3>;
-    hipLaunchKernelGGL(retry_kernel, dim3(rg), dim3(kThreads), 0, s->stream,
-                       s->d_data, s->d_offsets, s->d_ivs, s->n_ivs,
-                       s->d_aux, s->d_rk_save,
-                       s->d_partials + s->n_partials * kPartialStride,
-                       s->d_heads, s->d_walked, nullptr, 0, s->ivb,
-                       n_bat, bat_lo, s->d_retry, s->d_retry_n);
+    if (use_known) {
+      // join, then a small launch drains the batches the set did not
+      // predict (after the join: it shares the per-thread key save area
+      // with the known-list launch)
+      HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_join, 0));
+      const int lg = std::min(rg, 64);
+      launch_list(s->stream, lg,
+                  region1 + (uint64_t)rg * (kThreads / 64) * kPartialStride,
+                  s->d_retry, s->d_retry_n);
+      n_fold += (uint64_t)(rg + lg) * (kThreads / 64);
+    } else {
+      // retry pass: the general kernel over the aborted batch list
+      launch_list(s->stream, rg, region1, s->d_retry, s->d_retry_n);
+      n_fold += (uint64_t)rg * (kThreads / 64);
+    }
   } else {
     auto launch = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(s->grid), dim3(kThreads), 0, s->stream,
@@ -1803,13 +2120,18 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
     else launch(k_scan<8, 3>);
   }
   HIP_TRY(hipEventRecord(s->ev_mid, s->stream));
-  hipLaunchKernelGGL(k_reduce_pre, dim3(1024), dim3(256), 0, s->stream,
-                     s->dspec, s->d_partials, 2 * s->n_partials, s->d_heads,
-                     s->d_walked, n_bat, s->hstride, s->d_chunk);
-  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, s->stream, s->dspec,
-                     s->d_chunk, 1024, s->d_heads, s->d_cont, 0,
-                     s->d_result);
+  hipLaunchKernelGGL(k_fold, dim3(kFoldGrid), dim3(kFoldThreads), 0,
+                     s->stream, s->dspec, s->d_partials, n_fold, s->d_heads,
+                     s->d_walked, n_bat, s->hstride, s->d_chunk,
+                     s->d_fold_ticket, s->d_result);
   HIP_TRY(hipEventRecord(s->ev_end, s->stream));
+  if (usefast) {
+    // the abort count comes back with the result (pinned, no extra sync)
+    HIP_TRY(hipMemcpyAsync(s->h_retry_n, s->d_retry_n,
+                           sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           s->stream));
+    s->retry_pending = true;
+  }
   s->executed = true;
   return 0;
 }
@@ -1829,6 +2151,17 @@ int yb_gpu_scan_wait(ybg_scan_t* s) {
   HIP_TRY(hipEventElapsedTime(&ms2, s->ev_start, s->ev_end));
   s->last_decode_ms = ms1;
   s->last_total_ms = ms2;
+  if (s->retry_pending) {
+    s->retry_pending = false;
+    const uint64_t n_late = *s->h_retry_n;
+    s->last_retry_batches = s->last_known_n + n_late;
+    // late aborts are merged into the set; a first execute creates it
+    if (s->last_learn && (n_late || !s->known_valid ||
+                          !(s->known_key == s->last_key))) {
+      int rc = known_learn(s, n_late);
+      if (rc) return rc;
+    }
+  }
   return 0;
 }
 
@@ -2109,6 +2442,15 @@ int yb_gpu_scan_staged(ybg_scan_t* s) { return s->staged_last ? 1 : 0; }
 
 int yb_gpu_scan_planned(ybg_scan_t* s) { return s->planned_last ? 1 : 0; }
 
+int yb_gpu_scan_retry_batches(ybg_scan_t* s, uint64_t* n_out) {
+  *n_out = 0;
+  if (s->bloom_rejected || !s->executed) return 0;
+  int rc = yb_gpu_scan_wait(s);
+  if (rc) return rc;
+  *n_out = s->last_retry_batches;
+  return 0;
+}
+
 int yb_gpu_scan_close(ybg_scan_t* s) {
   if (s->stage_snap) yb_gpu_snapshot_close(s->stage_snap);
   if (s->d_data_owned && s->d_data) HIP_WARN(hipFree(s->d_data));
@@ -2122,6 +2464,14 @@ int yb_gpu_scan_close(ybg_scan_t* s) {
   if (s->d_cont) HIP_WARN(hipFree(s->d_cont));
   if (s->d_result) HIP_WARN(hipFree(s->d_result));
   if (s->d_chunk) HIP_WARN(hipFree(s->d_chunk));
+  if (s->d_fold_ticket) HIP_WARN(hipFree(s->d_fold_ticket));
+  if (s->d_walked) HIP_WARN(hipFree(s->d_walked));
+  if (s->d_retry) HIP_WARN(hipFree(s->d_retry));
+  if (s->d_retry_n) HIP_WARN(hipFree(s->d_retry_n));
+  if (s->h_retry_n) HIP_WARN(hipHostFree(s->h_retry_n));
+  if (s->d_known) HIP_WARN(hipFree(s->d_known));
+  if (s->d_known_n) HIP_WARN(hipFree(s->d_known_n));
+  if (s->d_known_bits) HIP_WARN(hipFree(s->d_known_bits));
   if (s->d_flags_all) HIP_WARN(hipFree(s->d_flags_all));
   if (s->d_em_sort) HIP_WARN(hipFree(s->d_em_sort));
   if (s->d_em_key) HIP_WARN(hipFree(s->d_em_key));
@@ -2146,6 +2496,9 @@ int yb_gpu_scan_close(ybg_scan_t* s) {
   if (s->ev_start) HIP_WARN(hipEventDestroy(s->ev_start));
   if (s->ev_mid) HIP_WARN(hipEventDestroy(s->ev_mid));
   if (s->ev_end) HIP_WARN(hipEventDestroy(s->ev_end));
+  if (s->ev_fork) HIP_WARN(hipEventDestroy(s->ev_fork));
+  if (s->ev_join) HIP_WARN(hipEventDestroy(s->ev_join));
+  if (s->stream2) HIP_WARN(hipStreamDestroy(s->stream2));
   if (s->stream) HIP_WARN(hipStreamDestroy(s->stream));
   delete s;
   return 0;

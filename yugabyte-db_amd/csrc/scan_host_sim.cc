@@ -149,9 +149,23 @@ int ybg_sim_scan(const ybg_scan_spec_t* spec, const uint8_t* data,
 // scan_one_interval as the per-batch fallback (the retry protocol the GPU
 // dispatch uses). n_fallback_out reports how many batches aborted — tests
 // assert 0 on eligible data and bit-exact results either way.
-int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
-                      const uint64_t* offsets, uint64_t n_blocks,
-                      ybg_scan_result_t* out, uint64_t* n_fallback_out) {
+// Head rows follow the kernels' state-byte protocol: batch b sits in lane
+// b % 64; the planned pass resolves a head inside the wave (head_action,
+// the kernel's own decision) when the predecessor lane completed on the
+// fast path, every other head is left pending and folded by state, as
+// k_fold does.
+// A known abort set (known_ids, any order, ids past the batch count
+// ignored) models the GPU dispatch's remembered set: listed batches go
+// straight to the general scanner, every other batch that aborts still
+// falls back, so the result never depends on the set. fallback_ids_out
+// (capacity fallback_cap) receives the ids of all batches the general
+// scanner ran, ascending.
+int ybg_sim_scan_fast_known(const ybg_scan_spec_t* spec, const uint8_t* data,
+                            const uint64_t* offsets, uint64_t n_blocks,
+                            const uint64_t* known_ids, uint64_t n_known,
+                            ybg_scan_result_t* out, uint64_t* n_fallback_out,
+                            uint64_t* fallback_ids_out,
+                            uint64_t fallback_cap) {
   DevSpec d;
   std::vector<unsigned char> aux;
   build_spec(spec, &d, &aux);
@@ -165,7 +179,11 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
   uint64_t entries = 0, scanned = 0, matched = 0, fallbacks = 0;
   uint64_t agg_val[2] = {0, 0}, agg_cnt[2] = {0, 0};
   std::vector<HeadOut<2>> heads(n_b);
-  std::vector<uint8_t> walked(n_b, 0);
+  std::vector<uint8_t> state(n_b, 0);    // the per-batch state byte
+  std::vector<uint8_t> fast_ok(n_b, 0);  // completed by scan_batch_fast
+  std::vector<uint8_t> known(n_b, 0);    // the bitmap k_scan_fast tests
+  for (uint64_t i = 0; i < n_known; ++i)
+    if (known_ids[i] < n_b) known[known_ids[i]] = 1;
   alignas(8) uint8_t key[kKeyCap];
   alignas(8) uint8_t rk_save[kKeyCap];
   uint64_t bht[6] = {0, 0, 0, 0, 0, 0};
@@ -195,7 +213,9 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
     const std::true_type plan_on{};
     const std::false_type plan_off{};
     int rc;
-    if (planned) {
+    if (known[b]) {
+      rc = 0;  // skipped by the fast kernel, run from the known list
+    } else if (planned) {
       switch (fast_plan_nr(plan)) {
         case 0: rc = call_fast(integral_constant<int, 0>{}, plan_on); break;
         case 1: rc = call_fast(integral_constant<int, 1>{}, plan_on); break;
@@ -210,6 +230,8 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
       rc = call_fast(integral_constant<int, 8>{}, plan_off);
     }
     if (!rc) {
+      if (fallback_ids_out && fallbacks < fallback_cap)
+        fallback_ids_out[fallbacks] = b;
       ++fallbacks;
       uint64_t av8[YBG_MAX_AGGS] = {0}, ac8[YBG_MAX_AGGS] = {0};
       HeadOut<YBG_MAX_AGGS> ho8;
@@ -229,11 +251,32 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
     entries += e32;
     scanned += s32;
     matched += m32;
-    walked[b] = wn ? 1 : 0;
+    fast_ok[b] = rc ? 1 : 0;
+    const uint8_t w = wn ? kBatchWalked : 0;
+    if (rc && planned) {
+      // k_scan_fast<PLAN>: the lane relay (lane 0's shuffle input is unused)
+      const bool p_ok = b > 0 && fast_ok[b - 1];
+      const bool p_wn = b > 0 && (state[b - 1] & kBatchWalked);
+      const HeadAction act =
+          head_action((unsigned)(b % 64), true, p_ok, p_wn);
+      if (act == kHeadFold) {
+        scanned += heads[b].scanned;
+        matched += heads[b].matched;
+        for (int g = 0; g < 2; ++g) {
+          agg_val[g] += heads[b].val[g];
+          agg_cnt[g] += heads[b].cnt[g];
+        }
+      }
+      state[b] = w | (act == kHeadWrite ? kBatchHeadPending : 0);
+    } else {
+      // interpreted fast kernel and the general (retry) kernel
+      state[b] = w | kBatchHeadPending;
+    }
   }
+  // k_fold: pending heads the predecessor did not walk into
   for (uint64_t b = 0; b < n_b; ++b) {
-    bool consumed = b > 0 && walked[b - 1];
-    if (consumed) continue;
+    if (!(state[b] & kBatchHeadPending)) continue;
+    if (b > 0 && (state[b - 1] & kBatchWalked)) continue;
     scanned += heads[b].scanned;
     matched += heads[b].matched;
     for (int g = 0; g < d.num_aggs && g < 2; ++g)
@@ -245,6 +288,13 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
   return 0;
 }
 
+int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
+                      const uint64_t* offsets, uint64_t n_blocks,
+                      ybg_scan_result_t* out, uint64_t* n_fallback_out) {
+  return ybg_sim_scan_fast_known(spec, data, offsets, n_blocks, nullptr, 0,
+                                 out, n_fallback_out, nullptr, 0);
+}
+
 // 1 when ybg_sim_scan_fast would run this spec through the planned pass
 // (build_fast_plan succeeds and YBG_PLAN does not turn it off), else 0 —
 // the simulator-side yb_gpu_scan_planned.
@@ -254,6 +304,11 @@ int ybg_sim_scan_planned(const ybg_scan_spec_t* spec) {
   build_spec(spec, &d, &aux);
   FastPlan plan;
   return build_fast_plan(d, &plan) && fast_plan_enabled() ? 1 : 0;
+}
+
+// TEST ONLY: the planned kernel's per-lane head decision (head_action).
+int ybg_sim_head_action(unsigned lane, int ok, int p_ok, int p_wn) {
+  return (int)head_action(lane, ok != 0, p_ok != 0, p_wn != 0);
 }
 
 // TEST ONLY: the planned pass's column extraction (plan_load_cols) over a
