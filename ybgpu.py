@@ -800,6 +800,35 @@ def sim_scan_fast_known(spec, data, offsets, n_blocks, known_ids):
         cap = nf.value
 
 
+def sim_fast_census(spec, data, offsets, n_blocks, max_blocks=0):
+    """Per-trip census of the fast kernel's entry loop over the first
+    max_blocks blocks (0 = all), 64 consecutive batches replayed in lockstep
+    as one wave (ybg_sim_fast_census) — MEASUREMENT TOOL. Returns a dict of
+    counters plus the sp / ns1 / ns2 histograms of the delta entries."""
+    f = _sig(product(), "ybg_sim_fast_census", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
+              C.POINTER(C.c_uint64)])
+    out = (C.c_uint64 * 208)()
+    rc = f(C.byref(spec), data, offsets, n_blocks, max_blocks, out)
+    if rc != 0:
+        raise RuntimeError(f"ybg_sim_fast_census failed rc={rc}")
+    kinds = ("switch", "restart", "frequent", "c211", "general")
+    c = {"waves": out[0], "batches": out[1], "aborted": out[2],
+         "wave_trips": out[3], "lane_trips": out[4],
+         "wave_delta_trips": out[10], "wave_multi_path_trips": out[11],
+         "tail_iters_lockstep": out[17], "tail_iters_lanes": out[18],
+         "lds_iters_lockstep": out[19], "lds_iters_lanes": out[20],
+         "lane_delta_entries": out[21]}
+    for i, k in enumerate(kinds):
+        c["wave_trips_" + k] = out[5 + i]
+        c["lane_trips_" + k] = out[12 + i]
+    c["sp_hist"] = {i: out[32 + i] for i in range(128) if out[32 + i]}
+    c["ns1_hist"] = {i: out[160 + i] for i in range(32) if out[160 + i]}
+    c["ns2_hist"] = {i: out[192 + i] for i in range(16) if out[192 + i]}
+    return c
+
+
 def sim_scan_planned(spec):
     """True when sim_scan_fast runs this spec through the planned
     packed-row pass (column plan built and YBG_PLAN not 0) — the

@@ -1736,7 +1736,7 @@ DEV void acc_row(const DevSpec& sp, const RowCtxT<NA>& rc, uint64_t* agg_val,
         agg_val[g] += 1;
         break;
       case YBG_AGG_SUM_INT64:
-        agg_val[g] = (uint64_t)((int64_t)agg_val[g] + (int64_t)v);
+        agg_val[g] += v;  // wrapping int64 sum: same bits, unsigned add
         break;
       case YBG_AGG_SUM_DOUBLE: {
         double cur = __longlong_as_double((long long)agg_val[g]) +
@@ -1776,7 +1776,7 @@ DEV void combine1(int op, uint64_t* av, uint64_t* ac, uint64_t bv,
     case YBG_AGG_COUNT_STAR:
     case YBG_AGG_COUNT:
     case YBG_AGG_SUM_INT64:
-      *av = (uint64_t)((int64_t)*av + (int64_t)bv);
+      *av += bv;  // wrapping int64 sum: same bits, unsigned add
       break;
     case YBG_AGG_SUM_DOUBLE: {
       double cur = (*ac ? __longlong_as_double((long long)*av) : 0.0) +
@@ -2560,7 +2560,7 @@ DEV void combine_datum(int op, uint64_t* val, uint64_t* cnt, uint64_t v) {
       *val += 1;
       break;
     case YBG_AGG_SUM_INT64:
-      *val = (uint64_t)((int64_t)*val + (int64_t)v);
+      *val += v;  // wrapping int64 sum: same bits, unsigned add
       break;
     case YBG_AGG_SUM_DOUBLE: {
       double cur = __longlong_as_double((long long)*val) +
@@ -2778,6 +2778,13 @@ DEV void plan_load_cols(const OffT* off, const uint8_t* value, uint64_t* uv) {
 #ifndef YBG_FABORT
 #define YBG_FABORT(n) return 0
 #endif
+// Per-trip census hook of scan_batch_fast: empty unless the host simulator
+// defines it before including this header (kind 0 interval switch, 1
+// restart, 2 frequent, 3 case 2.1.1, 4 general form; then sp, ns1, ns2 and
+// the two LDS byte-loop trip counts).
+#ifndef YBG_CENSUS_REC
+#define YBG_CENSUS_REC(kind, sp, ns1, ns2, l1, l2) ((void)0)
+#endif
 
 // Returns 1 = batch done (accumulators updated), 0 = abort (accumulators
 // and ho untouched except bht[3..5] restart candidates, which are benign
@@ -2890,6 +2897,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       const uint8_t* np = nblk + nx.start;
       limit = nblk + nx.end;
       blk = nblk;
+      YBG_CENSUS_REC(0, 0, 0, 0, 0, 0);
       if (np != p) {
         p = np;
         rdr.init(p);
@@ -2955,6 +2963,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       er.shared = 0;
       q = er.value + value_size;
       rdr.seek(er.value);
+      YBG_CENSUS_REC(1, 0, ns1, 0, 0, 0);
     } else {
       // Unified STABLE-LENGTH delta decode: frequent, 2.1.1 (d2 == 0) and
       // the general form with last8 reuse and zero deltas
@@ -2984,6 +2993,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       const uint32_t value_size = (uint32_t)(e1 >> 2);
       const uint64_t inc = (e1 & 2) << 7;
       uint32_t ns1, ns2, hl, sp;
+      int form;  // census only: 2 frequent, 3 case 2.1.1, 4 general
       uint64_t w2 = rdr.peek8_at(8);
       auto hdr_byte = [&](uint32_t j) -> uint32_t {
         return (uint32_t)((j < 8 ? (w >> (8 * j)) : (w2 >> (8 * (j - 8)))) &
@@ -2995,6 +3005,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         ns1 = 1;
         ns2 = 1;
         hl = e1len + 1;
+        form = 2;
       } else {
         uint32_t e2 = hdr_byte(e1len);
         if ((e2 & 3) == 1) {  // case 2.1.1; d2 != 0 changes the length
@@ -3004,6 +3015,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
           sp = hdr_byte(e1len + 1);
           if (sp & 0x80) YBG_FABORT(11);
           hl = e1len + 2;
+          form = 3;
         } else if ((e2 & 7) == 7 && !(e2 & 40)) {
           // general form: reuse8 set, ns1_delta and ns2_delta absent
           uint32_t o = e1len + 1;
@@ -3019,6 +3031,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
           sp = hdr_byte(o);
           if (sp & 0x80) YBG_FABORT(14);
           hl = o + 1;
+          form = 4;
         } else {
           YBG_FABORT(15);  // restart mid-interval / delta forms: general path
         }
@@ -3056,6 +3069,8 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         uint32_t lds_n = sp < rkb ? (rkb - sp < ns1 ? rkb - sp : ns1) : 0;
         uint32_t lds2 = ns2s < rkb ? (rkb - ns2s < ns2 ? rkb - ns2s : ns2)
                                    : 0;
+        YBG_CENSUS_REC(form, sp, ns1, ns2, FUSE ? ns1 : lds_n,
+                       FUSE ? ns2 : lds2);
         if constexpr (FUSE) {
           // MVCC shape: one pass per changed byte, LDS write
           // unconditional (key bytes >= rkb are dead on this path — only
@@ -3088,6 +3103,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         }
       }
       (void)inc;
+      (void)form;
       rdr.consume(nb);
       er.value = rdr.pos();
       er.value_len = value_size;

@@ -74,6 +74,10 @@ __device__ __forceinline__ void batch_bounds(
   if (*hi > n_ivs) *hi = n_ivs;
 }
 
+__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int off) {
+  return (uint64_t)__shfl_down((unsigned long long)v, off);
+}
+
 // Wave restart-minimum into the wave's partial record, run by lane 0:
 // lane l's candidate {hi, lo, len} sits at slots[(tid + l) * stride + off]
 // (cold: len == 0 for every lane unless track_restart saw candidates).
@@ -352,9 +356,56 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
   }
 
   // errs = 0: the fast scanner aborts a batch instead of failing it
-  __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
-  wave_fold_partials<NA>(sp, entries, scanned, matched, 0, agg_val, agg_cnt,
-                         red_val, red_cnt, rmin_scratch, 3, 0, partials);
+  if constexpr (PLAN) {
+    // Every plan slot is a wrapping 64-bit add (the in-wave head fold above
+    // already depends on it), so a shuffle tree gives the bits the serial
+    // lane-order fold gave: no LDS round trip, no barrier, no operator
+    // switch. Same record layout, k_fold reads it unchanged.
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      entries += __shfl_down(entries, off);
+      scanned += __shfl_down(scanned, off);
+      matched += __shfl_down(matched, off);
+#pragma unroll
+      for (int g = 0; g < NA; ++g) {
+        agg_val[g] += shfl_down_u64(agg_val[g], off);
+        agg_cnt[g] += shfl_down_u64(agg_cnt[g], off);
+      }
+    }
+    const unsigned lane = threadIdx.x & 63;
+    const uint64_t wave_id =
+        ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
+    uint64_t* prec = partials + wave_id * kPartialStride;
+    if (lane == 0) {
+      prec[0] = entries;
+      prec[1] = scanned;
+      prec[2] = matched;
+      prec[3] = 0;
+#pragma unroll
+      for (int g = 0; g < NA; ++g) {
+        // slots the query does not use stay as the serial fold leaves them
+        if (g >= sp.num_aggs) continue;
+        prec[4 + 2 * g] = agg_val[g];
+        prec[4 + 2 * g + 1] = agg_cnt[g];
+      }
+    }
+    // restart minimum: cold, a candidate exists only when track_restart saw
+    // one. Lane 0 reads slots its own wave's lanes wrote, so a wave-scope
+    // fence orders them; no workgroup barrier.
+    if (__any(rmin[2] != 0)) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (lane == 0) wave_restart_min(rmin_scratch, 3, 0, prec);
+    } else if (lane == 0) {
+      prec[4 + 2 * YBG_MAX_AGGS] = 0;
+      prec[4 + 2 * YBG_MAX_AGGS + 1] = 0;
+      prec[4 + 2 * YBG_MAX_AGGS + 2] = 0;
+    }
+  } else {
+    __shared__ uint64_t red_val[kThreads], red_cnt[kThreads];
+    wave_fold_partials<NA>(sp, entries, scanned, matched, 0, agg_val,
+                           agg_cnt, red_val, red_cnt, rmin_scratch, 3, 0,
+                           partials);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -641,10 +692,6 @@ __device__ __forceinline__ void fold_record(const DevSpec& sp, bool restart,
     const int rb = 4 + 2 * YBG_MAX_AGGS;
     fold_restart(a, r[rb], r[rb + 1], r[rb + 2]);
   }
-}
-
-__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int off) {
-  return (uint64_t)__shfl_down((unsigned long long)v, off);
 }
 
 // Workgroup reduction of every thread's accumulator into thread 0's:

@@ -7,6 +7,19 @@
 extern "C" unsigned long long ybg_fast_abort_hist[32];
 extern "C" unsigned long long ybg_fast_abort_hist[32] = {0};
 #define YBG_FABORT(n) do { ++ybg_fast_abort_hist[n]; return 0; } while (0)
+// Per-trip census of scan_batch_fast (ybg_sim_fast_census): one record per
+// loop trip while a sink is installed, nothing otherwise.
+struct YbgCensusRec { unsigned char kind, sp, ns1, ns2, l1, l2; };
+struct YbgCensusSink { YbgCensusRec* rec; unsigned n, cap; };
+static YbgCensusSink* ybg_census_sink = nullptr;
+#define YBG_CENSUS_REC(kind_, sp_, ns1_, ns2_, l1_, l2_)                     \
+  do {                                                                       \
+    if (ybg_census_sink && ybg_census_sink->n < ybg_census_sink->cap)        \
+      ybg_census_sink->rec[ybg_census_sink->n++] = YbgCensusRec{             \
+          (unsigned char)(kind_), (unsigned char)(sp_),                      \
+          (unsigned char)(ns1_), (unsigned char)(ns2_),                      \
+          (unsigned char)(l1_), (unsigned char)(l2_)};                       \
+  } while (0)
 #define YBG_HOST_SIM 1
 #define YBG_DEV_QUAL inline
 #include "scan_device.h"
@@ -90,6 +103,44 @@ void store_result(const DevSpec& d, uint64_t entries, uint64_t scanned,
         break;
     }
   }
+}
+
+// One batch through scan_batch_fast in the shape the GPU dispatch picks:
+// NC, FUSE and PLAN mirror it so CPU fuzz covers every compiled shape of
+// the fast kernel.
+int fast_batch(const DevSpec& d, const FastPlan& plan, bool planned,
+               const uint8_t* data, const uint64_t* offsets,
+               const Interval* ivs, uint64_t n_ivs, uint64_t lo, uint64_t hi,
+               uint8_t* key, uint64_t* rmin, uint32_t* e32, uint32_t* s32,
+               uint32_t* m32, uint64_t* agg_val, uint64_t* agg_cnt,
+               HeadOut<2>* ho, bool* wn) {
+  auto call_fast = [&](auto nc_tag, auto plan_tag) {
+    constexpr int N = decltype(nc_tag)::value;
+    constexpr bool P = decltype(plan_tag)::value;
+    auto run = [&](auto fuse_tag) {
+      constexpr bool F = decltype(fuse_tag)::value;
+      return scan_batch_fast<2, N, F, P>(d, data, offsets, ivs, n_ivs, lo, hi,
+                                         key, rmin, e32, s32, m32, agg_val,
+                                         agg_cnt, ho, wn, &plan);
+    };
+    return d.fuse_hint ? run(std::true_type{}) : run(std::false_type{});
+  };
+  using std::integral_constant;
+  const std::true_type plan_on{};
+  const std::false_type plan_off{};
+  if (planned) {
+    switch (fast_plan_nr(plan)) {
+      case 0: return call_fast(integral_constant<int, 0>{}, plan_on);
+      case 1: return call_fast(integral_constant<int, 1>{}, plan_on);
+      case 2: return call_fast(integral_constant<int, 2>{}, plan_on);
+      case 3: return call_fast(integral_constant<int, 3>{}, plan_on);
+      case 4: return call_fast(integral_constant<int, 4>{}, plan_on);
+      default: return call_fast(integral_constant<int, 8>{}, plan_on);
+    }
+  }
+  if (d.num_value_cols <= 4)
+    return call_fast(integral_constant<int, 4>{}, plan_off);
+  return call_fast(integral_constant<int, 8>{}, plan_off);
 }
 }  // namespace
 
@@ -195,40 +246,11 @@ int ybg_sim_scan_fast_known(const ybg_scan_spec_t* spec, const uint8_t* data,
     uint32_t e32 = 0, s32 = 0, m32 = 0;
     uint64_t lo = b * ivb;
     uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
-    // NC, FUSE and PLAN mirror the GPU dispatch so CPU fuzz covers every
-    // compiled shape of the fast kernel
-    auto call_fast = [&](auto nc_tag, auto plan_tag) {
-      constexpr int N = decltype(nc_tag)::value;
-      constexpr bool P = decltype(plan_tag)::value;
-      auto run = [&](auto fuse_tag) {
-        constexpr bool F = decltype(fuse_tag)::value;
-        return scan_batch_fast<2, N, F, P>(d, data, offsets, ivs.data(),
-                                           n_ivs, lo, hi, key, bht + 3, &e32,
-                                           &s32, &m32, agg_val, agg_cnt,
-                                           &heads[b], &wn, &plan);
-      };
-      return d.fuse_hint ? run(std::true_type{}) : run(std::false_type{});
-    };
-    using std::integral_constant;
-    const std::true_type plan_on{};
-    const std::false_type plan_off{};
-    int rc;
-    if (known[b]) {
-      rc = 0;  // skipped by the fast kernel, run from the known list
-    } else if (planned) {
-      switch (fast_plan_nr(plan)) {
-        case 0: rc = call_fast(integral_constant<int, 0>{}, plan_on); break;
-        case 1: rc = call_fast(integral_constant<int, 1>{}, plan_on); break;
-        case 2: rc = call_fast(integral_constant<int, 2>{}, plan_on); break;
-        case 3: rc = call_fast(integral_constant<int, 3>{}, plan_on); break;
-        case 4: rc = call_fast(integral_constant<int, 4>{}, plan_on); break;
-        default: rc = call_fast(integral_constant<int, 8>{}, plan_on); break;
-      }
-    } else if (d.num_value_cols <= 4) {
-      rc = call_fast(integral_constant<int, 4>{}, plan_off);
-    } else {
-      rc = call_fast(integral_constant<int, 8>{}, plan_off);
-    }
+    int rc = 0;  // known: skipped by the fast kernel, run from the list
+    if (!known[b])
+      rc = fast_batch(d, plan, planned, data, offsets, ivs.data(), n_ivs, lo,
+                      hi, key, bht + 3, &e32, &s32, &m32, agg_val, agg_cnt,
+                      &heads[b], &wn);
     if (!rc) {
       if (fallback_ids_out && fallbacks < fallback_cap)
         fallback_ids_out[fallbacks] = b;
@@ -293,6 +315,97 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
                       ybg_scan_result_t* out, uint64_t* n_fallback_out) {
   return ybg_sim_scan_fast_known(spec, data, offsets, n_blocks, nullptr, 0,
                                  out, n_fallback_out, nullptr, 0);
+}
+
+// Census of the fast kernel's entry loop (scripts/fast_census.py): replays
+// the first max_blocks blocks (0 = all) through scan_batch_fast with the
+// per-trip hook on, 64 consecutive batches at a time, and counts them the
+// way a wave runs them — trip t of the wave holds every lane's trip t, a
+// path costs the wave a pass when ANY lane takes it, and a byte loop runs
+// to the longest lane's count. out[] (kCensusWords u64):
+//   0 waves, 1 batches, 2 aborted batches, 3 wave trips, 4 lane trips,
+//   5..9 wave trips holding kind 0..4 (switch, restart, frequent, 2.1.1,
+//   general), 10 wave trips holding a delta entry, 11 wave trips holding
+//   two or more of {restart, frequent/2.1.1, general}, 12..16 lane trips
+//   per kind, 17 / 18 tail-patch iterations lockstep / summed over lanes,
+//   19 / 20 the same for the LDS byte loops, 21 lane delta entries,
+//   32.. sp histogram (128), 160.. ns1 (32), 192.. ns2 (16) over lane
+//   delta entries.
+enum { kCensusWords = 208 };
+int ybg_sim_fast_census(const ybg_scan_spec_t* spec, const uint8_t* data,
+                        const uint64_t* offsets, uint64_t n_blocks,
+                        uint64_t max_blocks, uint64_t* out) {
+  DevSpec d;
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
+  if (!fast_eligible(d)) return 9;
+  if (max_blocks && max_blocks < n_blocks) n_blocks = max_blocks;
+  std::vector<Interval> ivs;
+  if (int rc = build_intervals(data, offsets, n_blocks, &ivs)) return rc;
+  const uint64_t n_ivs = ivs.size();
+  const uint64_t ivb = sim_ivb();
+  const uint64_t n_b = (n_ivs + ivb - 1) / ivb;
+  FastPlan plan;
+  const bool planned = build_fast_plan(d, &plan) && fast_plan_enabled();
+  memset(out, 0, kCensusWords * sizeof(uint64_t));
+  const unsigned kCap = 1u << 16;
+  std::vector<YbgCensusRec> recs(64 * (size_t)kCap);
+  alignas(8) uint8_t key[kKeyCap];
+  for (uint64_t w0 = 0; w0 < n_b; w0 += 64) {
+    unsigned cnt[64] = {0};
+    unsigned max_n = 0;
+    const unsigned lanes = (unsigned)(n_b - w0 < 64 ? n_b - w0 : 64);
+    for (unsigned l = 0; l < lanes; ++l) {
+      const uint64_t b = w0 + l;
+      const uint64_t lo = b * ivb;
+      const uint64_t hi = lo + ivb < n_ivs ? lo + ivb : n_ivs;
+      YbgCensusSink sink = {recs.data() + (size_t)l * kCap, 0, kCap};
+      uint32_t e32 = 0, s32 = 0, m32 = 0;
+      uint64_t av[2] = {0, 0}, ac[2] = {0, 0}, rmin[3] = {0, 0, 0};
+      HeadOut<2> ho;
+      bool wn = false;
+      ybg_census_sink = &sink;
+      const int rc = fast_batch(d, plan, planned, data, offsets, ivs.data(),
+                                n_ivs, lo, hi, key, rmin, &e32, &s32, &m32,
+                                av, ac, &ho, &wn);
+      ybg_census_sink = nullptr;
+      if (!rc) out[2] += 1;
+      cnt[l] = sink.n;
+      if (sink.n > max_n) max_n = sink.n;
+    }
+    out[0] += 1;
+    out[1] += lanes;
+    out[3] += max_n;
+    for (unsigned t = 0; t < max_n; ++t) {
+      unsigned kinds = 0, m1 = 0, m2 = 0, ml1 = 0, ml2 = 0;
+      for (unsigned l = 0; l < lanes; ++l) {
+        if (t >= cnt[l]) continue;
+        const YbgCensusRec& r = recs[(size_t)l * kCap + t];
+        out[4] += 1;
+        out[12 + r.kind] += 1;
+        kinds |= 1u << r.kind;
+        if (r.kind < 2) continue;
+        out[21] += 1;
+        out[18] += (uint64_t)r.ns1 + r.ns2;
+        out[20] += (uint64_t)r.l1 + r.l2;
+        out[32 + (r.sp & 127)] += 1;
+        out[160 + (r.ns1 & 31)] += 1;
+        out[192 + (r.ns2 & 15)] += 1;
+        if (r.ns1 > m1) m1 = r.ns1;
+        if (r.ns2 > m2) m2 = r.ns2;
+        if (r.l1 > ml1) ml1 = r.l1;
+        if (r.l2 > ml2) ml2 = r.l2;
+      }
+      for (int k = 0; k < 5; ++k) out[5 + k] += (kinds >> k) & 1;
+      if (kinds & 0x1c) out[10] += 1;
+      const int paths = ((kinds >> 1) & 1) + ((kinds & 0xc) ? 1 : 0) +
+                        ((kinds >> 4) & 1);
+      if (paths >= 2) out[11] += 1;
+      out[17] += m1 + m2;
+      out[19] += ml1 + ml2;
+    }
+  }
+  return 0;
 }
 
 // 1 when ybg_sim_scan_fast would run this spec through the planned pass
