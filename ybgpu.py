@@ -819,7 +819,8 @@ def sim_fast_census(spec, data, offsets, n_blocks, max_blocks=0):
          "wave_delta_trips": out[10], "wave_multi_path_trips": out[11],
          "tail_iters_lockstep": out[17], "tail_iters_lanes": out[18],
          "lds_iters_lockstep": out[19], "lds_iters_lanes": out[20],
-         "lane_delta_entries": out[21]}
+         "lane_delta_entries": out[21],
+         "restart_ns1_min": out[22], "restart_ns1_max": out[23]}
     for i, k in enumerate(kinds):
         c["wave_trips_" + k] = out[5 + i]
         c["lane_trips_" + k] = out[12 + i]
@@ -836,6 +837,17 @@ def sim_scan_planned(spec):
     f = _sig(product(), "ybg_sim_scan_planned", C.c_int,
              [C.POINTER(ScanSpec)])
     return bool(f(C.byref(spec)))
+
+
+PLAN_SHAPE_PAIR, PLAN_SHAPE_PAIR_SINGLE, PLAN_SHAPE_TWO_PAIRS = 16, 17, 18
+
+
+def sim_plan_shape(spec):
+    """The compiled shape of the spec's column plan: the ranged-column count
+    of the two-list form (0..4, 8), one of the grouped PLAN_SHAPE_* codes, or
+    -1 without a plan (ybg_sim_plan_shape). TEST INFRASTRUCTURE."""
+    f = _sig(product(), "ybg_sim_plan_shape", C.c_int, [C.POINTER(ScanSpec)])
+    return f(C.byref(spec))
 
 
 HEAD_NONE, HEAD_FOLD, HEAD_WRITE = 0, 1, 2

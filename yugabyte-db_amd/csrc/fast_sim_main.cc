@@ -5,7 +5,9 @@
 // tests/fast_header_cases.py — row counts around the interval and block
 // sizes, small tablets that mix the delta forms, a one-column schema with a
 // short value, five-version rows at two read times, builder tablets that
-// abort batches, one batch per row — with every tablet copied into an
+// abort batches, one batch per row, and tablets whose last entry is a
+// restart entry (a packed row whose last column is summed; a lone
+// tombstone) for the 16-byte loads — with every tablet copied into an
 // allocation of EXACTLY total + 48 bytes (the tail slack the scanner's
 // loads are allowed), so a header or value load that reaches further than
 // the contract — today's register window, or any direct-load form that
@@ -145,9 +147,13 @@ int check_generated(const char* tag, int ncols, uint64_t rows, int versions,
 
 // Builder tablets over the one- or four-column schema. kind: 0 row
 // tombstones, 1 column updates mid-batch, 2 one batch per row with operands
-// near INT64_MAX, 3 the same with one record above the read time.
+// near INT64_MAX, 3 the same with one record above the read time, 4 four
+// columns (r * 8 + c) at one batch per row, so that the tablet's last entry
+// is a restart entry whose packed row ends the entry area and whose last
+// column the headline query sums, 5 the same with a lone row tombstone (a
+// one-byte value) as that last restart entry.
 int check_built(const char* tag, int kind, uint64_t rows, const Query& q) {
-  const int ncols = kind == 1 ? 4 : 1;
+  const int ncols = (kind == 1 || kind >= 4) ? 4 : 1;
   ybg_schema_t schema = make_schema(ncols);
   ybg_builder_t* b = ybg_builder_create(&schema, YBG_ENC_THREE_SHARED_PARTS,
                                         4096, kind >= 2 ? 1 : 16);
@@ -174,6 +180,13 @@ int check_built(const char* tag, int kind, uint64_t rows, const Query& q) {
       if (r % 37 == 20)
         rc = ybg_builder_add_column_update(b, &k, 2, 3000ull << 12, 0, seq++,
                                            r + 5, nullptr, 0, 0);
+    } else if (kind >= 4) {
+      for (int c = 0; c < 4; ++c) v.datums[c] = r * 8 + c;
+      ht = 1000;
+      if (kind == 5 && r + 1 == rows) {
+        rc = ybg_builder_add_row_tombstone(b, &k, ht << 12, 0, seq++);
+        continue;
+      }
     } else {
       v.datums[0] = kind == 2 ? (uint64_t)INT64_MAX - r * 3 : r;
       ht = (kind == 3 && r == 137) ? 3000 : 1000;
@@ -239,6 +252,18 @@ int main() {
   for (uint64_t n : {1, 63, 64, 65, 255, 256, 257})
     bad |= check_built("epilogue", 2, n, count_sum0);
   bad |= check_built("restart-one", 3, 200, restart);
+  // the 16-byte loads at the end of the buffer: the restart decode's key
+  // chunks and the planned pass's pair over the row's last two columns
+  Query wide = headline;
+  wide.num_preds = 3;
+  wide.preds[0] = {0, 0, YBG_PRED_GE, 8, nullptr, 0};
+  wide.preds[1] = {0, 1, YBG_PRED_LT, 8 * 90, nullptr, 0};
+  wide.preds[2] = {0, 2, YBG_PRED_GE, 18, nullptr, 0};
+  wide.read = wide.local = 5000;
+  for (uint64_t n : {1, 2, 93, 94, 200}) {
+    bad |= check_built("last-restart-sum-last-column", 4, n, wide);
+    bad |= check_built("last-restart-tombstone", 5, n, wide);
+  }
   printf(bad ? "FAILED\n" : "all ok\n");
   return bad;
 }

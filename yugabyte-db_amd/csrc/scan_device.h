@@ -333,6 +333,48 @@ DEV uint64_t load_u64_direct_g(const uint8_t* p) {
   return u;
 #endif
 }
+// The same for 16 bytes: one global_load_dwordx4 reading exactly
+// [p, p+16) at any byte address.
+struct U64x2 {
+  uint64_t lo, hi;
+};
+DEV U64x2 load_u128_direct_g(const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  typedef u64x2 __attribute__((aligned(1))) u64x2_a1;
+  const u64x2 v = *(const __attribute__((address_space(1))) u64x2_a1*)p;
+  return U64x2{v.x, v.y};
+#else
+  U64x2 u;
+  memcpy(&u, p, 16);
+  return u;
+#endif
+}
+// The fast kernel's per-lane LDS key slot, read and written through an LDS
+// address-space pointer: ds_read / ds_write (lgkmcnt only) where the
+// generic pointer gives flat_load / flat_store, whose wait also drains the
+// global loads in flight. p is a slot base plus a multiple of 8 (the slot
+// array is 16-byte aligned and kFastKeyCap is a multiple of 16). In the
+// host simulator it is a plain pointer.
+DEV uint64_t lds_load_u64(const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const __attribute__((address_space(3))) uint64_t*)p;
+#else
+  uint64_t u;
+  memcpy(&u, p, 8);
+  return u;
+#endif
+}
+DEV void lds_store_u128(uint8_t* p, U64x2 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __attribute__((address_space(3))) uint64_t* q =
+      (__attribute__((address_space(3))) uint64_t*)p;
+  q[0] = v.lo;
+  q[1] = v.hi;
+#else
+  memcpy(p, &v, 16);
+#endif
+}
 DEV uint64_t load_be64(const uint8_t* p) {
   return __builtin_bswap64(load_u64_una(p));
 }
@@ -2647,26 +2689,58 @@ inline bool fast_eligible(const DevSpec& d) {
 //                     unsatisfiable set is lo = INT64_MAX, hi = INT64_MIN,
 //                     which the same two compares reject for every value.
 //   operand columns — per aggregate slot, the offset of the column it sums.
-// A column that is both is loaded once per list (the second load hits the
-// line the first one fetched).
+// A counting slot (COUNT, COUNT(*)) has no operand and causes no load.
+//
+// Grouped shapes. Every lane reads its own cache line, so what a row costs
+// is the number of load instructions, not their width. When the live
+// columns (ranged ∪ SUM operands, each once, sorted by offset) fall into
+// at most two load groups with at least one 16-byte pair — two live 8-byte
+// columns whose offsets differ by exactly 8, read by one direct 16-byte
+// load of exactly those bytes — the plan is compiled as groups instead of
+// the two lists: pairs first, then single 8-byte groups. Each 8 bytes
+// loaded is a slot with its own range (the full range for a slot that is
+// only summed), and an aggregate picks its operand by a per-slot mask. The
+// compiled shapes are (pairs, singles) = (1,0), (1,1), (2,0); any other
+// plan keeps the two lists, where a column that is both ranged and summed
+// is loaded once per list (the second load hits the line the first one
+// fetched).
 // ---------------------------------------------------------------------------
 constexpr int kPlanMaxCols = 8;  // fast_eligible's column cap
 constexpr int kPlanAggs = 2;     // the fast kernel's aggregate slots
+constexpr int kPlanGroupSlots = 4;  // most slots of a grouped shape
+// shape codes of the planned kernel's NC parameter: 0..4 and 8 are the
+// ranged-column count of the two-list form, these are the grouped shapes
+constexpr int kPlanShapeP1 = 16;    // one pair
+constexpr int kPlanShapeP1S1 = 17;  // one pair, one single
+constexpr int kPlanShapeP2 = 18;    // two pairs
+constexpr int plan_np(int nc) {
+  return nc == kPlanShapeP2 ? 2 : (nc >= kPlanShapeP1 ? 1 : 0);
+}
+constexpr int plan_ns(int nc) {
+  return nc < kPlanShapeP1 ? nc : (nc == kPlanShapeP1S1 ? 1 : 0);
+}
 
 struct FastPlan {
-  // ranged column k < n_rng; slots [n_rng, 8) are padding that always
-  // passes (full range, offset 0) so a kernel compiled for more ranged
-  // columns than the query has needs no guard
+  // two-list form: ranged column k < n_rng; slots [n_rng, 8) are padding
+  // that always passes (full range, offset 0) so a kernel compiled for more
+  // ranged columns than the query has needs no guard. Grouped shapes:
+  // lo / hi per SLOT (both halves of each pair, then the singles), off per
+  // load GROUP (pairs, then singles); n_rng keeps the ranged-column count.
   int64_t lo[kPlanMaxCols], hi[kPlanMaxCols];
   uint8_t off[kPlanMaxCols];      // byte offset from the value start
   uint32_t n_rng;
   // aggregate slot g (all zero for g >= num_aggs): val += (operand &
   // agg_mask) + agg_one, cnt += agg_on
-  uint32_t agg_off[kPlanAggs];    // operand's byte offset (0 = none: the
-                                  // load is masked out)
+  uint32_t agg_off[kPlanAggs];    // operand's byte offset (two-list form;
+                                  // not loaded when agg_mask is 0)
   uint32_t agg_mask[kPlanAggs];   // ~0u SUM_INT64, 0 COUNT / COUNT(*)
   uint32_t agg_one[kPlanAggs];    // 1 COUNT / COUNT(*), 0 SUM_INT64
   uint32_t agg_on[kPlanAggs];     // 1 when the slot is in use
+  // the compiled shape (fast_plan_nr): n_rng up to 4, then 8, or one of the
+  // grouped shapes below
+  uint32_t shape;
+  // grouped shapes only: ~0u at the slot whose 8 bytes aggregate g sums
+  uint32_t agg_sel[kPlanAggs][kPlanGroupSlots];
   // the per-entry spec fields of the fast shape, so the hot loop reads no
   // constant memory at all
   uint32_t rkb, v2_fixed_len, track_restart;
@@ -2747,14 +2821,73 @@ inline bool build_fast_plan(const DevSpec& d, FastPlan* pl) {
   pl->v2_fixed_len = d.v2_fixed_len;
   pl->track_restart = (uint32_t)d.track_restart;
   pl->reg_lim = d.reg_lim;
+  pl->shape = pl->n_rng <= 4 ? pl->n_rng : (uint32_t)kPlanMaxCols;
+  // load groups over the live columns, each once, sorted by offset
+  struct Live {
+    uint32_t off;
+    int64_t lo, hi;
+  };
+  Live lv[kPlanMaxCols + kPlanAggs];
+  int n = 0;
+  for (uint32_t k = 0; k < pl->n_rng; ++k)
+    lv[n++] = Live{pl->off[k], pl->lo[k], pl->hi[k]};
+  for (int g = 0; g < d.num_aggs; ++g) {
+    if (!pl->agg_mask[g]) continue;  // counts: no operand
+    bool have = false;
+    for (int i = 0; i < n; ++i) have |= lv[i].off == pl->agg_off[g];
+    if (!have) lv[n++] = Live{pl->agg_off[g], INT64_MIN, INT64_MAX};
+  }
+  for (int i = 1; i < n; ++i)
+    for (int j = i; j > 0 && lv[j].off < lv[j - 1].off; --j) {
+      const Live t = lv[j];
+      lv[j] = lv[j - 1];
+      lv[j - 1] = t;
+    }
+  Live pr[kPlanMaxCols + kPlanAggs], sg[kPlanMaxCols + kPlanAggs];
+  int np = 0, ns = 0;
+  for (int i = 0; i < n;) {
+    if (i + 1 < n && lv[i + 1].off == lv[i].off + 8) {
+      pr[2 * np] = lv[i];
+      pr[2 * np + 1] = lv[i + 1];
+      ++np;
+      i += 2;
+    } else {
+      sg[ns++] = lv[i++];
+    }
+  }
+  const int shape = (np == 1 && ns == 0)   ? kPlanShapeP1
+                    : (np == 1 && ns == 1) ? kPlanShapeP1S1
+                    : (np == 2 && ns == 0) ? kPlanShapeP2
+                                           : -1;
+  if (shape >= 0) {
+    // slots: both halves of each pair, then the singles; off[] holds one
+    // offset per GROUP
+    for (int k = 0; k < kPlanMaxCols; ++k) {
+      pl->lo[k] = INT64_MIN;
+      pl->hi[k] = INT64_MAX;
+      pl->off[k] = 0;
+    }
+    Live slot[kPlanGroupSlots];
+    for (int k = 0; k < 2 * np; ++k) slot[k] = pr[k];
+    for (int k = 0; k < ns; ++k) slot[2 * np + k] = sg[k];
+    for (int k = 0; k < np; ++k) pl->off[k] = (uint8_t)pr[2 * k].off;
+    for (int k = 0; k < ns; ++k) pl->off[np + k] = (uint8_t)sg[k].off;
+    for (int k = 0; k < 2 * np + ns; ++k) {
+      pl->lo[k] = slot[k].lo;
+      pl->hi[k] = slot[k].hi;
+      for (int g = 0; g < d.num_aggs; ++g)
+        if (pl->agg_mask[g] && pl->agg_off[g] == slot[k].off)
+          pl->agg_sel[g][k] = ~0u;
+    }
+    pl->shape = (uint32_t)shape;
+  }
   return true;
 }
 
-// The planned kernel's compile-time ranged-column count for a plan: exact
-// up to 4, then 8 (padding slots always pass).
-inline int fast_plan_nr(const FastPlan& pl) {
-  return pl.n_rng <= 4 ? (int)pl.n_rng : kPlanMaxCols;
-}
+// The planned kernel's compile-time shape for a plan: the ranged-column
+// count of the two-list form, exact up to 4, then 8 (padding slots always
+// pass), or a grouped shape code.
+inline int fast_plan_nr(const FastPlan& pl) { return (int)pl.shape; }
 
 // YBG_PLAN=0 keeps a plannable spec on the interpreted fast kernel (the
 // GPU dispatch and the simulator read the same knob).
@@ -2773,6 +2906,22 @@ template <int N, class OffT>
 DEV void plan_load_cols(const OffT* off, const uint8_t* value, uint64_t* uv) {
 #pragma unroll
   for (int k = 0; k < N; ++k) uv[k] = load_u64_direct_g(value + off[k]);
+}
+// The same for a grouped shape: NP 16-byte pairs, then NS single 8-byte
+// groups, into 2 * NP + NS slots. Every group is real, so each load reads
+// exactly its columns' bytes inside the row.
+template <int NP, int NS>
+DEV void plan_load_groups(const uint8_t* off, const uint8_t* value,
+                          uint64_t* uv) {
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const U64x2 v = load_u128_direct_g(value + off[k]);
+    uv[2 * k] = v.lo;
+    uv[2 * k + 1] = v.hi;
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k)
+    uv[2 * NP + k] = load_u64_direct_g(value + off[NP + k]);
 }
 
 #ifndef YBG_FABORT
@@ -2806,8 +2955,9 @@ DEV void plan_load_cols(const OffT* off, const uint8_t* value, uint64_t* uv) {
 // compiled column plan *pl (build_fast_plan) instead of interpreting sp;
 // everything else — entry decode, visibility, row splitting, head/walk and
 // the abort protocol — is the same code. pl is only read when PLAN, and
-// NC is then the number of RANGED columns the pass evaluates
-// (fast_plan_nr: 0..4 or 8), not the schema's column cap.
+// NC is then the plan's shape (fast_plan_nr): the number of RANGED columns
+// the pass evaluates, 0..4 or 8, or a grouped shape code — not the
+// schema's column cap.
 template <int NA, int NC, bool FUSE = false, bool PLAN = false>
 DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
                         const uint64_t* block_offsets, const Interval* ivs,
@@ -2818,7 +2968,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
                         uint64_t* agg_cnt, HeadOut<NA>* ho,
                         bool* walked_next_out,
                         const FastPlan* pl = nullptr) {
-  static_assert(!PLAN || (NA == kPlanAggs && NC <= kPlanMaxCols),
+  static_assert(!PLAN || (NA == kPlanAggs &&
+                          (NC <= kPlanMaxCols ||
+                           (NC >= kPlanShapeP1 && NC <= kPlanShapeP2))),
                 "plan shape");
   Interval iv = ivs[j_lo];
   const uint8_t* blk = data + block_offsets[iv.block];
@@ -2913,7 +3065,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // tail needs ukey >= 16) abort to the general path.
       at_restart = false;
       if (limit - p < 3) YBG_FABORT(1);
-      uint64_t w = load_u64_una_g(p);
+      // one direct load of exactly [p, p+8): at least 3 of the bytes are
+      // the entry's, the rest lie in the block or the buffer's tail slack
+      uint64_t w = load_u64_direct_g(p);
       uint32_t b0 = (uint32_t)(w & 0xff);
       uint64_t e1;
       uint32_t e1len;
@@ -2931,38 +3085,64 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       uint32_t e2 = (uint32_t)((w >> (8 * e1len)) & 0xff);
       if (e2 & 1) YBG_FABORT(4);  // reuse forms: not a self-contained restart
       uint32_t ns1 = e2 >> 1;
-      // upper bound: the u64-chunk copy below writes up to ns1 rounded up
-      // to 8 into the caller's kFastKeyCap LDS slot
+      // upper bound: the 16-byte chunk copy below writes up to ns1 rounded
+      // up to 16 into the caller's kFastKeyCap LDS slot, and kFastKeyCap -
+      // 8 = 72 rounds up to 80 = kFastKeyCap, the slot exactly
+      static_assert(kFastKeyCap % 16 == 0, "chunk copy fills whole chunks");
       if (ns1 < 24 || ns1 > kFastKeyCap - 8) YBG_FABORT(5);
       uint32_t hl = e1len + 1;
       if ((uint64_t)(limit - p) < (uint64_t)hl + ns1 + value_size) YBG_FABORT(6);
       const uint8_t* kp2 = p + hl;
-      // row-change detection: compare the first rkb bytes before copying
-      kchg = !row_open;
-      if (row_open) {
-        uint32_t full = rkb & ~7u;
-        for (uint32_t i = 0; i < full; i += 8)
-          if (load_u64_una(&key[i]) != load_u64_una_g(kp2 + i)) kchg = true;
-        if (rkb & 7) {
-          uint64_t m = (1ull << (8 * (rkb & 7))) - 1;
-          if (((load_u64_una(&key[full]) ^ load_u64_una_g(kp2 + full)) & m))
-            kchg = true;
-        }
-      }
-      for (uint32_t i = 0; i < ns1; i += 8) {
-        uint64_t w8 = load_u64_una_g(kp2 + i);
-        __builtin_memcpy(&key[i], &w8, 8);
-      }
+      // Every remaining load of the entry issues here in one batch, before
+      // the first use of any of them: the key in direct 16-byte chunks (two
+      // always, ns1 >= 24; a third for keys past 32 bytes; a loop only past
+      // 48), the two tail words, and the reader's window at the value. A
+      // chunk is loaded only when it starts inside the key, so it reads at
+      // most 15 bytes past the key's end: the entry's value, the block's
+      // next bytes, or at the buffer's end its tail slack.
+      const U64x2 c0 = load_u128_direct_g(kp2);
+      const U64x2 c1 = load_u128_direct_g(kp2 + 16);
+      U64x2 c2{0, 0};
+      if (ns1 > 32) c2 = load_u128_direct_g(kp2 + 32);
+      thi = __builtin_bswap64(load_u64_direct_g(kp2 + ns1 - 24));
+      tlo = __builtin_bswap64(load_u64_direct_g(kp2 + ns1 - 16));
       key_len = ns1;
-      // the key bytes still sit in the block data: tail_from_lds's two
-      // loads, over global memory
-      thi = __builtin_bswap64(load_u64_una_g(kp2 + ns1 - 24));
-      tlo = __builtin_bswap64(load_u64_una_g(kp2 + ns1 - 16));
       er.value = kp2 + ns1;
       er.value_len = value_size;
       er.shared = 0;
       q = er.value + value_size;
       rdr.seek(er.value);
+      // row-change detection: the first rkb bytes of those same registers
+      // against the previous key in the LDS slot, before the chunks
+      // overwrite it. A key too short to hold rkb bytes compares bytes that
+      // are not its own, as before; check 19 below aborts it whatever kchg
+      // says.
+      auto word_chg = [&](uint32_t i, uint64_t nw) -> bool {
+        if (i >= rkb) return false;  // uniform: rkb is a plan constant
+        const uint64_t m =
+            rkb - i >= 8 ? ~0ull : (1ull << (8 * (rkb - i))) - 1;
+        return ((lds_load_u64(&key[i]) ^ nw) & m) != 0;
+      };
+      kchg = !row_open;
+      if (row_open) {
+        kchg |= word_chg(0, c0.lo);
+        kchg |= word_chg(8, c0.hi);
+        kchg |= word_chg(16, c1.lo);
+        kchg |= word_chg(24, c1.hi);
+        kchg |= word_chg(32, c2.lo);
+        kchg |= word_chg(40, c2.hi);
+      }
+      lds_store_u128(&key[0], c0);
+      lds_store_u128(&key[16], c1);
+      if (ns1 > 32) lds_store_u128(&key[32], c2);
+      for (uint32_t i = 48; i < ns1; i += 16) {
+        const U64x2 c = load_u128_direct_g(kp2 + i);
+        if (row_open) {
+          kchg |= word_chg(i, c.lo);
+          kchg |= word_chg(i + 8, c.hi);
+        }
+        lds_store_u128(&key[i], c);
+      }
       YBG_CENSUS_REC(1, 0, ns1, 0, 0, 0);
     } else {
       // Unified STABLE-LENGTH delta decode: frequent, 2.1.1 (d2 == 0) and
@@ -3186,13 +3366,39 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
             // planned pass: every live-column load, then two compares
             // per ranged column — no predicate loop, no dtype / operator /
             // width dispatch, no branch
-            uint64_t uv[NC > 0 ? NC : 1];
-            plan_load_cols<NC>(pl->off, value, uv);
-            plan_load_cols<NA>(pl->agg_off, value, agg_datum);
+            constexpr int NP = plan_np(NC), NS = plan_ns(NC);
+            constexpr int NSL = 2 * NP + NS;  // slots
+            uint64_t uv[NSL > 0 ? NSL : 1];
+            if constexpr (NP > 0) {
+              plan_load_groups<NP, NS>(pl->off, value, uv);
+            } else {
+              plan_load_cols<NC>(pl->off, value, uv);
+              // a counting slot has no operand: no load (uniform, the mask
+              // is a plan constant; acc_row masks the stale register out)
 #pragma unroll
-            for (int k = 0; k < NC; ++k) {
+              for (int g = 0; g < NA; ++g)
+                if (pl->agg_mask[g])
+                  agg_datum[g] = load_u64_direct_g(value + pl->agg_off[g]);
+            }
+#pragma unroll
+            for (int k = 0; k < NSL; ++k) {
               const int64_t v = (int64_t)uv[k];
               row_pass &= (v >= pl->lo[k]) & (v <= pl->hi[k]);
+            }
+            if constexpr (NP > 0) {
+              // the operand is the one slot its mask selects (none for a
+              // counting slot)
+#pragma unroll
+              for (int g = 0; g < NA; ++g) {
+                uint32_t dl = 0, dh = 0;
+#pragma unroll
+                for (int k = 0; k < NSL; ++k) {
+                  const uint32_t m = pl->agg_sel[g][k];
+                  dl |= (uint32_t)uv[k] & m;
+                  dh |= (uint32_t)(uv[k] >> 32) & m;
+                }
+                agg_datum[g] = ((uint64_t)dh << 32) | dl;
+              }
             }
           } else {
             // fixed-offset column extraction (decode_packed_v2_fixed, lean

@@ -262,7 +262,10 @@ __global__ __launch_bounds__(kThreads, WPS) void k_scan_fast(
   const DevSpec& sp = c_spec;
   const FastPlan* pl = nullptr;
   if constexpr (PLAN) pl = &plan;
-  __shared__ uint8_t key_scratch[kThreads * kFastKeyCap];
+  // 16-byte aligned: the restart decode reads and writes a lane's slot in
+  // aligned 8- and 16-byte LDS accesses (kFastKeyCap is a multiple of 16)
+  __shared__ __attribute__((aligned(16))) uint8_t
+      key_scratch[kThreads * kFastKeyCap];
   __shared__ uint64_t rmin_scratch[kThreads * 3];
   uint8_t* key = key_scratch + (size_t)threadIdx.x * kFastKeyCap;
   uint64_t* rmin = rmin_scratch + (size_t)threadIdx.x * 3;
@@ -2124,6 +2127,15 @@ int yb_gpu_scan_execute(ybg_scan_t* s) {
         case 2: launchp(std::integral_constant<int, 2>{}); break;
         case 3: launchp(std::integral_constant<int, 3>{}); break;
         case 4: launchp(std::integral_constant<int, 4>{}); break;
+        case kPlanShapeP1:
+          launchp(std::integral_constant<int, kPlanShapeP1>{});
+          break;
+        case kPlanShapeP1S1:
+          launchp(std::integral_constant<int, kPlanShapeP1S1>{});
+          break;
+        case kPlanShapeP2:
+          launchp(std::integral_constant<int, kPlanShapeP2>{});
+          break;
         default: launchp(std::integral_constant<int, 8>{}); break;
       }
     } else if (fuse) {

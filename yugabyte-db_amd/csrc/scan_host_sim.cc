@@ -135,6 +135,12 @@ int fast_batch(const DevSpec& d, const FastPlan& plan, bool planned,
       case 2: return call_fast(integral_constant<int, 2>{}, plan_on);
       case 3: return call_fast(integral_constant<int, 3>{}, plan_on);
       case 4: return call_fast(integral_constant<int, 4>{}, plan_on);
+      case kPlanShapeP1:
+        return call_fast(integral_constant<int, kPlanShapeP1>{}, plan_on);
+      case kPlanShapeP1S1:
+        return call_fast(integral_constant<int, kPlanShapeP1S1>{}, plan_on);
+      case kPlanShapeP2:
+        return call_fast(integral_constant<int, kPlanShapeP2>{}, plan_on);
       default: return call_fast(integral_constant<int, 8>{}, plan_on);
     }
   }
@@ -329,6 +335,7 @@ int ybg_sim_scan_fast(const ybg_scan_spec_t* spec, const uint8_t* data,
 //   two or more of {restart, frequent/2.1.1, general}, 12..16 lane trips
 //   per kind, 17 / 18 tail-patch iterations lockstep / summed over lanes,
 //   19 / 20 the same for the LDS byte loops, 21 lane delta entries,
+//   22 / 23 shortest / longest restart key (ns1 of kind 1; 0 = none),
 //   32.. sp histogram (128), 160.. ns1 (32), 192.. ns2 (16) over lane
 //   delta entries.
 enum { kCensusWords = 208 };
@@ -384,6 +391,10 @@ int ybg_sim_fast_census(const ybg_scan_spec_t* spec, const uint8_t* data,
         out[4] += 1;
         out[12 + r.kind] += 1;
         kinds |= 1u << r.kind;
+        if (r.kind == 1) {
+          if (!out[22] || r.ns1 < out[22]) out[22] = r.ns1;
+          if (r.ns1 > out[23]) out[23] = r.ns1;
+        }
         if (r.kind < 2) continue;
         out[21] += 1;
         out[18] += (uint64_t)r.ns1 + r.ns2;
@@ -417,6 +428,17 @@ int ybg_sim_scan_planned(const ybg_scan_spec_t* spec) {
   build_spec(spec, &d, &aux);
   FastPlan plan;
   return build_fast_plan(d, &plan) && fast_plan_enabled() ? 1 : 0;
+}
+
+// TEST ONLY: the compiled shape of the spec's column plan (fast_plan_nr:
+// 0..4 or 8 ranged columns of the two-list form, 16 one pair, 17 a pair
+// and a single, 18 two pairs), -1 when the spec has no plan.
+int ybg_sim_plan_shape(const ybg_scan_spec_t* spec) {
+  DevSpec d;
+  std::vector<unsigned char> aux;
+  build_spec(spec, &d, &aux);
+  FastPlan plan;
+  return build_fast_plan(d, &plan) ? fast_plan_nr(plan) : -1;
 }
 
 // TEST ONLY: the planned kernel's per-lane head decision (head_action).
