@@ -7,7 +7,10 @@
 // short value, five-version rows at two read times, builder tablets that
 // abort batches, one batch per row, and tablets whose last entry is a
 // restart entry (a packed row whose last column is summed; a lone
-// tombstone) for the 16-byte loads — with every tablet copied into an
+// tombstone) for the 16-byte loads, and for the pipelined trip version
+// chains with tombstones in front of full rows that end on a delta entry
+// with a one-byte value, and two key columns that make delta entries 16, 17
+// and 25 bytes long in front of the value — with every tablet copied into an
 // allocation of EXACTLY total + 48 bytes (the tail slack the scanner's
 // loads are allowed), so a header or value load that reaches further than
 // the contract — today's register window, or any direct-load form that
@@ -34,12 +37,13 @@ namespace {
 constexpr uint64_t kSlack = 48;
 constexpr uint64_t kMvccBase = 1600000000000000ull;
 
-ybg_schema_t make_schema(int ncols) {
+ybg_schema_t make_schema(int ncols, int nkeys = 1) {
   ybg_schema_t s;
   memset(&s, 0, sizeof(s));
   s.has_hash = 1;
   s.num_hash_cols = 1;
-  s.key_types[0] = YBG_KT_INT64;
+  s.num_range_cols = nkeys - 1;
+  for (int i = 0; i < nkeys; ++i) s.key_types[i] = YBG_KT_INT64;
   s.num_value_cols = ncols;
   for (int i = 0; i < ncols; ++i) s.value_cols[i] = {10 + i, YBG_T_INT64, 1};
   return s;
@@ -151,12 +155,19 @@ int check_generated(const char* tag, int ncols, uint64_t rows, int versions,
 // columns (r * 8 + c) at one batch per row, so that the tablet's last entry
 // is a restart entry whose packed row ends the entry area and whose last
 // column the headline query sums, 5 the same with a lone row tombstone (a
-// one-byte value) as that last restart entry.
+// one-byte value) as that last restart entry, 6 three-version chains of four
+// columns with tombstones in front of full rows (every third row deleted,
+// every fifth with a tombstone above the read time) that end the tablet on a
+// DELTA entry with a one-byte value, where the early column loads of the
+// pipelined trip must not issue, 7 two key columns that both change every
+// row, so that delta entries are 16, 17 and 25 bytes long in front of the
+// value (the entry window's second half, the tablet's last entry included).
 int check_built(const char* tag, int kind, uint64_t rows, const Query& q) {
   const int ncols = (kind == 1 || kind >= 4) ? 4 : 1;
-  ybg_schema_t schema = make_schema(ncols);
-  ybg_builder_t* b = ybg_builder_create(&schema, YBG_ENC_THREE_SHARED_PARTS,
-                                        4096, kind >= 2 ? 1 : 16);
+  ybg_schema_t schema = make_schema(ncols, kind == 7 ? 2 : 1);
+  ybg_builder_t* b = ybg_builder_create(
+      &schema, YBG_ENC_THREE_SHARED_PARTS, 4096,
+      (kind >= 2 && kind <= 5) ? 1 : 16);
   uint64_t seq = 1ull << 50;
   int rc = 0;
   for (uint64_t r = 0; r < rows && !rc; ++r) {
@@ -180,6 +191,26 @@ int check_built(const char* tag, int kind, uint64_t rows, const Query& q) {
       if (r % 37 == 20)
         rc = ybg_builder_add_column_update(b, &k, 2, 3000ull << 12, 0, seq++,
                                            r + 5, nullptr, 0, 0);
+    } else if (kind == 6) {
+      if (r + 1 == rows) {
+        rc = ybg_builder_add_row_tombstone(b, &k, 2000ull << 12, 0, seq++);
+        continue;
+      }
+      if (r % 5 == 1)
+        rc = ybg_builder_add_row_tombstone(b, &k, 9000ull << 12, 0, seq++);
+      if (!rc && r % 3 == 0)
+        rc = ybg_builder_add_row_tombstone(b, &k, 4000ull << 12, 0, seq++);
+      for (uint64_t ver = 3; ver >= 1 && !rc; --ver) {
+        for (int c = 0; c < 4; ++c) v.datums[c] = r * 8 + c + ver * 1000;
+        if (ver > 1)
+          rc = ybg_builder_add_packed_row(b, &k, (ver * 1000) << 12, 0, seq++,
+                                          2, &v);
+      }
+      ht = 1000;
+    } else if (kind == 7) {
+      k.datums[1] = r << 40;
+      for (int c = 0; c < 4; ++c) v.datums[c] = r * 8 + c;
+      ht = kMvccBase + r * 1000;
     } else if (kind >= 4) {
       for (int c = 0; c < 4; ++c) v.datums[c] = r * 8 + c;
       ht = 1000;
@@ -263,6 +294,19 @@ int main() {
   for (uint64_t n : {1, 2, 93, 94, 200}) {
     bad |= check_built("last-restart-sum-last-column", 4, n, wide);
     bad |= check_built("last-restart-tombstone", 5, n, wide);
+  }
+  // the pipelined trip: early column loads next to short values, and the
+  // entry window's second half, up to the end of the buffer
+  Query chains = wide, keys2 = wide;
+  chains.preds[1] = {0, 1, YBG_PRED_LT, 1ull << 40, nullptr, 0};
+  keys2.preds[1] = chains.preds[1];
+  keys2.read = keys2.local = kMvccBase + 1000000000ull;
+  for (uint64_t n : {2, 17, 33, 200}) {
+    for (uint64_t rd : {1500, 2500, 3500, 5000}) {
+      chains.read = chains.local = rd;
+      bad |= check_built("chains-tombstone-last", 6, n, chains);
+    }
+    bad |= check_built("two-keys-long-headers", 7, n, keys2);
   }
   printf(bad ? "FAILED\n" : "all ok\n");
   return bad;

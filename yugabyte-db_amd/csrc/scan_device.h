@@ -2958,6 +2958,24 @@ DEV void plan_load_groups(const uint8_t* off, const uint8_t* value,
 // NC is then the plan's shape (fast_plan_nr): the number of RANGED columns
 // the pass evaluates, 0..4 or 8, or a grouped shape code — not the
 // schema's column cap.
+// Trip order of the planned kernels (PIPE below). The entry's first 16
+// bytes are in registers when the trip starts (the window, one direct
+// 16-byte load at p issued by the trip before). The header parse gives nb
+// and value_size, so value = p + nb and q = value + value_size are
+// arithmetic, and right after abort check 17 the trip issues every load it
+// will need: the row's column groups (only where the value has the full
+// packed row's length, the row is new or has no visible version yet, and
+// !FUSE: on version chains most entries are not the first visible one and
+// time follows the load count) and the next entry's window at q. The
+// changed-byte loops, checks 19-23, visibility and the row boundary run
+// while they are in flight; the one wait of the trip stands in front of the
+// range compares. The early column loads are speculative on visibility and
+// on the value's header bytes, and read exactly the bytes the pass reads
+// later: inside [value, value + v2_fixed_len), which check 17 has placed
+// below the interval's limit. The window reads [q, q + 16), q <= limit:
+// the restart array, the next block or the buffer's tail slack. An entry
+// with nb > 13 (a changed hash) loads the window's second half,
+// [p + 16, p + 32), on the spot and waits for it.
 template <int NA, int NC, bool FUSE = false, bool PLAN = false>
 DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
                         const uint64_t* block_offsets, const Interval* ivs,
@@ -2977,8 +2995,14 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
   const uint8_t* p = blk + iv.start;
   const uint8_t* limit = blk + iv.end;
   uint64_t cur_iv = j_lo;
-  Rdr rdr;
-  rdr.init(p);
+  // PIPE: the pipelined trip (see the doc above). The kernels that run at
+  // four waves per SIMD keep the reader window and the serial order: the
+  // registers the loads in flight hold would cost them the fourth wave.
+  constexpr bool PIPE = PLAN && !(FUSE && NC == 0);
+  Rdr rdr;          // !PIPE: the reader window
+  U64x2 wa{0, 0};   // PIPE: the entry window, the 16 bytes [p, p + 16)
+  if constexpr (PIPE) wa = load_u128_direct_g(p);
+  else rdr.init(p);
   bool at_restart = true;  // interval starts are restart points
 
 #pragma unroll
@@ -3052,12 +3076,46 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       YBG_CENSUS_REC(0, 0, 0, 0, 0, 0);
       if (np != p) {
         p = np;
-        rdr.init(p);
+        if constexpr (PIPE) wa = load_u128_direct_g(p);
+        else rdr.init(p);
       }
       continue;
     }
     bool kchg;
     const uint8_t* q = nullptr;
+    // the first value bytes (vb0 and the packed-row header check read three)
+    uint32_t vw = 0;
+    // planned pass: the row's column slots and, in the two-list form, the
+    // SUM operands (into ad, not agg_datum: the row boundary still has the
+    // previous row to accumulate when a delta trip loads them early)
+    constexpr int NSL =
+        !PLAN ? 0 : plan_np(NC) > 0 ? 2 * plan_np(NC) + plan_ns(NC) : NC;
+    uint64_t uv[NSL > 0 ? NSL : 1];
+    uint64_t ad[NA];
+    bool cols_early = false;
+    (void)uv;
+    (void)ad;
+    auto load_cols = [&](const uint8_t* value) {
+      if constexpr (PLAN) {
+        constexpr int NP = plan_np(NC), NS = plan_ns(NC);
+        if constexpr (NP > 0) {
+          plan_load_groups<NP, NS>(pl->off, value, uv);
+        } else {
+          plan_load_cols<NC>(pl->off, value, uv);
+          // a counting slot has no operand: no load (uniform, the mask
+          // is a plan constant; acc_row masks the stale register out)
+#pragma unroll
+          for (int g = 0; g < NA; ++g) {
+            ad[g] = 0;
+            if (pl->agg_mask[g])
+              ad[g] = load_u64_direct_g(value + pl->agg_off[g]);
+          }
+        }
+      }
+    };
+    // the next entry's window, in flight from the moment its address is
+    // known until the bottom of the trip
+    U64x2 na{0, 0};
     if (YBG_UNLIKELY(at_restart)) {
       // compact restart decode: three_shared_parts no-reuse form
       // (block_builder_internal.h case 2.0; full key inline). Keys longer
@@ -3065,9 +3123,10 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // tail needs ukey >= 16) abort to the general path.
       at_restart = false;
       if (limit - p < 3) YBG_FABORT(1);
-      // one direct load of exactly [p, p+8): at least 3 of the bytes are
-      // the entry's, the rest lie in the block or the buffer's tail slack
-      uint64_t w = load_u64_direct_g(p);
+      // the window's first word, or one direct load of exactly [p, p+8): at
+      // least 3 of the bytes are the entry's, the rest lie in the block or
+      // the buffer's tail slack
+      uint64_t w = PIPE ? wa.lo : load_u64_direct_g(p);
       uint32_t b0 = (uint32_t)(w & 0xff);
       uint64_t e1;
       uint32_t e1len;
@@ -3096,7 +3155,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // Every remaining load of the entry issues here in one batch, before
       // the first use of any of them: the key in direct 16-byte chunks (two
       // always, ns1 >= 24; a third for keys past 32 bytes; a loop only past
-      // 48), the two tail words, and the reader's window at the value. A
+      // 48), the two tail words, and the reader's window at the value
+      // (PIPE: the value's first 8 bytes, [value, value + 8) <= limit + 8,
+      // and the next entry's window at q). A
       // chunk is loaded only when it starts inside the key, so it reads at
       // most 15 bytes past the key's end: the entry's value, the block's
       // next bytes, or at the buffer's end its tail slack.
@@ -3111,7 +3172,13 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       er.value_len = value_size;
       er.shared = 0;
       q = er.value + value_size;
-      rdr.seek(er.value);
+      uint64_t vq = 0;
+      if constexpr (PIPE) {
+        vq = load_u64_direct_g(er.value);
+        na = load_u128_direct_g(q);
+      } else {
+        rdr.seek(er.value);
+      }
       // row-change detection: the first rkb bytes of those same registers
       // against the previous key in the LDS slot, before the chunks
       // overwrite it. A key too short to hold rkb bytes compares bytes that
@@ -3143,6 +3210,8 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         }
         lds_store_u128(&key[i], c);
       }
+      if constexpr (PIPE) vw = (uint32_t)vq;
+      else vw = (uint32_t)rdr.peek8();
       YBG_CENSUS_REC(1, 0, ns1, 0, 0, 0);
     } else {
       // Unified STABLE-LENGTH delta decode: frequent, 2.1.1 (d2 == 0) and
@@ -3156,8 +3225,15 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // registers; bytes between rkb and the tail window need no store at
       // all (nothing reads them before the next restart overwrites).
       if (limit - p < 8) YBG_FABORT(7);
-      rdr.align8();  // body bytes peek up to 24 ahead of the position
-      uint64_t w = rdr.peek8();
+      uint64_t w, w2, w3 = 0, w4 = 0;
+      if constexpr (PIPE) {
+        w = wa.lo;
+        w2 = wa.hi;
+      } else {
+        rdr.align8();  // body bytes peek up to 24 ahead of the position
+        w = rdr.peek8();
+        w2 = rdr.peek8_at(8);
+      }
       uint32_t b0 = (uint32_t)(w & 0xff);
       uint64_t e1;
       uint32_t e1len;
@@ -3174,7 +3250,6 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       const uint64_t inc = (e1 & 2) << 7;
       uint32_t ns1, ns2, hl, sp;
       int form;  // census only: 2 frequent, 3 case 2.1.1, 4 general
-      uint64_t w2 = rdr.peek8_at(8);
       auto hdr_byte = [&](uint32_t j) -> uint32_t {
         return (uint32_t)((j < 8 ? (w >> (8 * j)) : (w2 >> (8 * (j - 8)))) &
                           0xff);
@@ -3230,15 +3305,44 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       // a ns2 range dipping below rkb implies sp < rkb (row change), so
       // kchg is already correct; those bytes just need LDS writes too
       kchg = sp < rkb || !row_open;
+      if constexpr (PIPE) {
+        // The window's second half, [p + 16, p + 32), only for an entry
+        // whose body or first three value bytes reach past byte 16 (a
+        // changed hash: the dominant entries have nb = 7 and 12)
+        if (YBG_UNLIKELY(nb > 13)) {
+          const U64x2 wb = load_u128_direct_g(p + 16);
+          w3 = wb.lo;
+          w4 = wb.hi;
+        }
+      }
+      const uint8_t* const value = p + nb;
+      q = value + value_size;
+      if constexpr (PIPE) {
+        // Every load of the trip issues here, as soon as its address is
+        // known and before the changed-byte loops: the row's columns (never
+        // for a value of another length: only a full packed row holds the
+        // plan's offsets) and the next entry's window. The columns are
+        // speculative on visibility and the value's header bytes, and are
+        // used only where the packed-row pass runs.
+        if constexpr (!FUSE) {
+          if (value_size == pl->v2_fixed_len && (kchg || !base_seen)) {
+            load_cols(value);
+            cols_early = true;
+          }
+        }
+        na = load_u128_direct_g(q);
+      }
       {
         // changed bytes: LDS only below rkb (the restart row-compare
         // source), register tail inside the window, nothing in between.
         // The tail is patched per byte from window bytes (needs align8 +
         // w3); range splices from loads or window peeks measured slower.
-        rdr.align8();
-        w = rdr.peek8();
-        w2 = rdr.peek8_at(8);
-        uint64_t w3 = rdr.peek8_at(16);
+        if constexpr (!PIPE) {
+          rdr.align8();
+          w = rdr.peek8();
+          w2 = rdr.peek8_at(8);
+          w3 = rdr.peek8_at(16);
+        }
         auto body_byte = [&](uint32_t j) -> uint8_t {
           uint64_t src = j < 8 ? w : (j < 16 ? w2 : w3);
           return (uint8_t)(src >> (8 * (j & 7)));
@@ -3284,10 +3388,19 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
       }
       (void)inc;
       (void)form;
-      rdr.consume(nb);
-      er.value = rdr.pos();
+      if constexpr (PIPE) {
+        // the value's first bytes: nb <= 24 keeps [nb, nb + 3) inside the
+        // window
+        const uint32_t wi = nb >> 3, sh = 8 * (nb & 7);
+        const uint64_t lo = wi == 0 ? w : wi == 1 ? w2 : wi == 2 ? w3 : w4;
+        const uint64_t hi = wi == 0 ? w2 : wi == 1 ? w3 : w4;
+        vw = (uint32_t)(sh ? (lo >> sh) | (hi << (64 - sh)) : lo);
+      } else {
+        rdr.consume(nb);
+        vw = (uint32_t)rdr.peek8();
+      }
+      er.value = value;
       er.value_len = value_size;
-      q = er.value + value_size;
     }
     const uint32_t ukey_len = key_len - 8;
     if (ukey_len < rkb + 2 || ukey_len < 16) YBG_FABORT(19);
@@ -3335,8 +3448,7 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
     e_b += (cur_iv < j_hi);
     walked |= (cur_iv == j_hi);
     // visibility (no intent-prefixed values in the fast shape)
-    const uint32_t vb0 =
-        er.value_len ? (uint32_t)(rdr.peek8() & 0xff) : 0u;
+    const uint32_t vb0 = er.value_len ? (vw & 0xff) : 0u;
     if (YBG_UNLIKELY(vb0 == kHybridTimeByte)) YBG_FABORT(23);
     const bool visible =
         u128_slice_cmp(ht_hi, ht_lo, ht_sz, reg_lim.hi, reg_lim.lo,
@@ -3359,26 +3471,20 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         if (YBG_LIKELY(er.value_len ==
                            (PLAN ? pl->v2_fixed_len : sp.v2_fixed_len) &&
                        vb0 == kPackedV2B &&
-                       (rdr.peek8() & 0xff8000u) == 0)) {
-          const uint8_t* value = rdr.pos();
-          rdr.seek(value + er.value_len);  // next window loads issue now
+                       (vw & 0xff8000u) == 0)) {
+          const uint8_t* value = er.value;
+          if constexpr (!PIPE) rdr.seek(q);  // next window loads issue now
           if constexpr (PLAN) {
-            // planned pass: every live-column load, then two compares
-            // per ranged column — no predicate loop, no dtype / operator /
-            // width dispatch, no branch
-            constexpr int NP = plan_np(NC), NS = plan_ns(NC);
-            constexpr int NSL = 2 * NP + NS;  // slots
-            uint64_t uv[NSL > 0 ? NSL : 1];
-            if constexpr (NP > 0) {
-              plan_load_groups<NP, NS>(pl->off, value, uv);
-            } else {
-              plan_load_cols<NC>(pl->off, value, uv);
-              // a counting slot has no operand: no load (uniform, the mask
-              // is a plan constant; acc_row masks the stale register out)
+            // planned pass: every live-column load (unless the trip issued
+            // them early), then two compares per ranged column — no
+            // predicate loop, no dtype / operator / width dispatch, no
+            // branch
+            constexpr int NP = plan_np(NC);
+            if (!cols_early) load_cols(value);
+            if constexpr (NP == 0) {
 #pragma unroll
               for (int g = 0; g < NA; ++g)
-                if (pl->agg_mask[g])
-                  agg_datum[g] = load_u64_direct_g(value + pl->agg_off[g]);
+                if (pl->agg_mask[g]) agg_datum[g] = ad[g];
             }
 #pragma unroll
             for (int k = 0; k < NSL; ++k) {
@@ -3459,8 +3565,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
             }
           }
           found = true;
+          if constexpr (PIPE) wa = na;
           p = q;
-          continue;  // reader already past the value
+          continue;  // !PIPE: the reader is already past the value
         } else if (er.value_len == 1 && vb0 == kTombB) {
           // row tombstone: row exists but is deleted (found stays false)
         } else {
@@ -3468,7 +3575,9 @@ DEV int scan_batch_fast(const DevSpec& sp, const uint8_t* data,
         }
       }
     }
-    rdr.seek(q);
+    // on to the entry at q: its window is in flight (PIPE) or loads now
+    if constexpr (PIPE) wa = na;
+    else rdr.seek(q);
     p = q;
   }
   // final open row
