@@ -84,6 +84,20 @@ def _lib():
         C.c_void_p, C.POINTER(y.SnapshotSelect), C.POINTER(C.c_uint64),
         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64,
         C.POINTER(y.SnapshotSelectResult)]
+    if hasattr(lib, "yb_gpu_snapshot_build_ex"):  # newer than the select
+        lib.yb_gpu_snapshot_build_ex.restype = C.c_int
+        lib.yb_gpu_snapshot_build_ex.argtypes = [
+            C.c_void_p, C.POINTER(y.SnapshotBuildOpts),
+            C.POINTER(C.c_void_p)]
+        lib.yb_gpu_snapshot_string_info.restype = C.c_int
+        lib.yb_gpu_snapshot_string_info.argtypes = [
+            C.c_void_p, C.POINTER(y.SnapshotStringInfo)]
+        lib.yb_gpu_snapshot_select_var.restype = C.c_int
+        lib.yb_gpu_snapshot_select_var.argtypes = [
+            C.c_void_p, C.POINTER(y.SnapshotSelect), C.POINTER(C.c_uint64),
+            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64,
+            C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64),
+            C.POINTER(y.SnapshotSelectResult)]
     lib.yb_gpu_snapshot_kernel_ms.restype = C.c_int
     lib.yb_gpu_snapshot_kernel_ms.argtypes = [C.c_void_p,
                                               C.POINTER(C.c_double)]
@@ -246,14 +260,22 @@ class GpuScan:
             "retry_batches")
         return n.value
 
-    def snapshot(self):
+    def snapshot(self, strings=False):
         """Build a columnar snapshot of the fed tablet at this handle's read
         time and bounds (yb_gpu_snapshot_build). The snapshot owns its
-        memory: it stays valid after this handle is closed."""
+        memory: it stays valid after this handle is closed. strings=True
+        stages the string value and key columns too
+        (yb_gpu_snapshot_build_ex with stage_strings)."""
         h = C.c_void_p()
-        self._check(self._lib.yb_gpu_snapshot_build(self._h, C.byref(h)),
-                    "snapshot_build")
-        return GpuSnapshot(self._lib, h)
+        if strings:
+            opts = y.SnapshotBuildOpts()
+            opts.stage_strings = 1
+            self._check(self._lib.yb_gpu_snapshot_build_ex(
+                self._h, C.byref(opts), C.byref(h)), "snapshot_build_ex")
+        else:
+            self._check(self._lib.yb_gpu_snapshot_build(self._h, C.byref(h)),
+                        "snapshot_build")
+        return GpuSnapshot(self._lib, h, self._spec.schema)
 
     def close(self):
         if self._h:
@@ -264,11 +286,13 @@ class GpuScan:
 class GpuSnapshot:
     """Columnar snapshot: the rows visible at one read time as dense
     device-resident column arrays, answering numeric predicate/aggregate
-    queries, GROUP BY and ordered row fetches with the streaming kernels."""
+    queries, GROUP BY and ordered row fetches with the streaming kernels;
+    built with strings=True also string predicates and string fetches."""
 
-    def __init__(self, lib, handle):
+    def __init__(self, lib, handle, schema=None):
         self._lib = lib
         self._h = handle
+        self._schema = schema  # tells select() which columns are strings
 
     def _check(self, rc, what):
         if rc:
@@ -281,6 +305,15 @@ class GpuSnapshot:
         out = y.SnapshotInfo()
         self._check(self._lib.yb_gpu_snapshot_info(self._h, C.byref(out)),
                     "snapshot_info")
+        return out
+
+    def string_info(self):
+        """Which string columns are staged and their heap bytes
+        (yb_gpu_snapshot_string_info); all zero without strings=True."""
+        out = y.SnapshotStringInfo()
+        self._check(
+            self._lib.yb_gpu_snapshot_string_info(self._h, C.byref(out)),
+            "snapshot_string_info")
         return out
 
     def query(self, preds, aggs):
@@ -365,13 +398,58 @@ class GpuSnapshot:
             raise err
         return datums, null_masks, row_ids, res
 
+    def select_var_raw(self, preds, cols, limit=0, backward=False, row_lo=0,
+                       row_hi=None, cap=1 << 16, varlen_cap=1 << 20):
+        """Row fetch with string projection (yb_gpu_snapshot_select_var):
+        select_raw's arrays plus the varlen heap and its size — (datums,
+        null_masks, row_ids, varlen, varlen_size, result). A projected
+        string column's datum is (len << 40) | offset into varlen, 0 for a
+        NULL. Errors raise GpuScanError with .code (8: cap or varlen_cap too
+        small), .result and .varlen_size (the heap size needed)."""
+        ncols = max(1, min(len(cols), y.MAX_SELECT_COLS))
+        sb = getattr(self, "_select_var_bufs", None)
+        if sb is None or sb[0] != (cap, ncols, varlen_cap):
+            n = max(cap, 1)
+            sb = ((cap, ncols, varlen_cap), (C.c_uint64 * (n * ncols))(),
+                  (C.c_uint32 * n)(), (C.c_uint64 * n)(),
+                  (C.c_uint8 * max(varlen_cap, 1))())
+            self._select_var_bufs = sb
+        datums, null_masks, row_ids, varlen = sb[1], sb[2], sb[3], sb[4]
+        q = y.snapshot_select(preds, cols, limit, backward, row_lo, row_hi)
+        res = y.SnapshotSelectResult()
+        vsize = C.c_uint64()
+        rc = self._lib.yb_gpu_snapshot_select_var(
+            self._h, C.byref(q), datums, null_masks, row_ids, cap, varlen,
+            varlen_cap, C.byref(vsize), C.byref(res))
+        if rc:
+            err = GpuScanError(
+                f"snapshot_select_var rc={rc}: "
+                f"{self._lib.yb_gpu_last_error().decode()}")
+            err.code = rc
+            err.result = res
+            err.varlen_size = vsize.value
+            raise err
+        return datums, null_masks, row_ids, varlen, vsize.value, res
+
     def select(self, preds, cols, limit=0, backward=False, row_lo=0,
-               row_hi=None, cap=1 << 16):
+               row_hi=None, cap=1 << 16, varlen_cap=1 << 20):
         """SELECT cols WHERE preds on the snapshot, in key order: returns
         (rows, result) with rows = [(projected values..., None for NULL)].
         cols: (is_key_col, col) pairs. Page with limit and
         result.resume_row (the next row_lo, or row_hi when backward) until
-        result.done."""
+        result.done. A projected string column (snapshot built with
+        strings=True) goes through select_var and comes back as bytes."""
+        strs = None
+        if self._schema is not None and len(cols) <= y.MAX_SELECT_COLS:
+            try:
+                strs = y.select_string_cols(self._schema, cols)
+            except IndexError:  # out of range: the ABI names the offender
+                strs = None
+        if strs and any(strs):
+            datums, null_masks, _ids, varlen, _vs, res = self.select_var_raw(
+                preds, cols, limit, backward, row_lo, row_hi, cap, varlen_cap)
+            return y.decode_snapshot_rows(res, datums, null_masks, len(cols),
+                                          cols, cap, varlen, strs), res
         datums, null_masks, _ids, res = self.select_raw(
             preds, cols, limit, backward, row_lo, row_hi, cap)
         return y.decode_snapshot_rows(res, datums, null_masks,

@@ -392,7 +392,9 @@ int yb_gpu_scan_retry_batches(ybg_scan_t *s, uint64_t *n_out);
  * (key columns indexed like ybg_row_batch_t.key_datums), one 8-byte datum
  * per row per column in the bit pattern yb_gpu_scan_next_batch delivers,
  * plus one uint32 null mask per row (ybg_row_batch_t.null_masks layout).
- * String columns are not staged. Rows are held in tablet key order.
+ * String columns are not staged unless the snapshot is built with
+ * yb_gpu_snapshot_build_ex and stage_strings (below). Rows are held in
+ * tablet key order.
  *
  *   yb_gpu_snapshot_build ~ DocRowwiseIterator ctor/Init + the full
  *                           FetchNext loop at the read point, with its
@@ -428,6 +430,46 @@ typedef struct {
   uint8_t  restart_ht[YBG_MAX_HT]; uint32_t restart_ht_len; /* as ybg_scan_result_t */
 } ybg_snapshot_info_t;
 int yb_gpu_snapshot_info(ybg_snapshot_t *sn, ybg_snapshot_info_t *out);
+
+/* Build with options. opts == NULL or stage_strings == 0 is exactly
+ * yb_gpu_snapshot_build (which is a call of this). With stage_strings every
+ * STRING value column and every STRING key column is staged too, key strings
+ * UNESCAPED, in the form yb_gpu_scan_next_batch delivers. Per staged string
+ * column the snapshot holds, in row order, n_rows + 1 uint64 byte offsets,
+ * the strings back to back, and one uint64 per row with the string's first
+ * 8 bytes (big-endian, zero padded) that the predicates stream; all three
+ * are a pure function of the rows. Errors: as yb_gpu_snapshot_build; 8 also
+ * when the strings exceed 2^40 bytes.
+ *
+ * On a string-staged snapshot yb_gpu_snapshot_query, _group_query, _select
+ * and _select_var additionally accept
+ *   - predicates GT, GE, LT, LE, EQ, NE and IN on staged string value and
+ *     key columns, in the block path's ABI form (compare: bytes / bytes_len
+ *     is the rhs; IN: bytes is a list of [u32 len][bytes] records; key
+ *     operands unescaped) and with its semantics: byte-wise unsigned memcmp
+ *     order, a proper prefix sorts first, a predicate on a NULL string
+ *     fails, the empty string is a value and not NULL;
+ *   - YBG_AGG_COUNT on a string value column (it reads only the null bit).
+ * Still error 9 there: IN_RANGE on a string column, SUM / MIN / MAX on a
+ * string column, a string GROUP BY column, and a string column in the
+ * projection of yb_gpu_snapshot_select (use yb_gpu_snapshot_select_var).
+ * ybg_snapshot_info_t.staged_value_cols keeps meaning "numeric staged";
+ * device_bytes includes the string storage. */
+typedef struct {
+  int32_t stage_strings;    /* 1: stage string value and key columns */
+  int32_t reserved[7];      /* must be zero */
+} ybg_snapshot_build_opts_t;
+int yb_gpu_snapshot_build_ex(ybg_scan_t *s, const ybg_snapshot_build_opts_t *opts,
+                             ybg_snapshot_t **out);
+
+typedef struct {
+  uint32_t staged_string_value_cols;  /* bit i: STRING value col i staged */
+  uint32_t staged_string_key_cols;    /* bit i: STRING key col i staged */
+  uint64_t string_bytes[YBG_MAX_COLS];        /* heap bytes per value column */
+  uint64_t key_string_bytes[YBG_MAX_KEYCOLS]; /* heap bytes per key column */
+} ybg_snapshot_string_info_t;
+/* All fields zero on a snapshot built without strings. */
+int yb_gpu_snapshot_string_info(ybg_snapshot_t *sn, ybg_snapshot_string_info_t *out);
 
 typedef struct {
   int32_t num_preds; ybg_pred_t preds[YBG_MAX_PREDS];
@@ -579,6 +621,29 @@ typedef struct {
 int yb_gpu_snapshot_select(ybg_snapshot_t *sn, const ybg_snapshot_select_t *q,
                            uint64_t *datums, uint32_t *null_masks, uint64_t *row_ids,
                            uint64_t cap, ybg_snapshot_select_result_t *out);
+/* The select with string projection, on a snapshot built with
+ * stage_strings. Everything documented for yb_gpu_snapshot_select holds
+ * (order, window, limit, paging, determinism, errors), plus:
+ * datums: a projected string column's datum is (len << 40) | offset into
+ *   varlen (the ybg_row_batch_t convention); a NULL is written as 0.
+ * varlen: [varlen_cap]. The heap is canonical: delivered rows in delivery
+ *   order, within a row the projected string columns in projection order
+ *   (a repeated column repeats its bytes), bytes back to back with no
+ *   padding. varlen[0 .. *varlen_size) is therefore a pure function of the
+ *   delivered rows: byte-identical across calls and across separately built
+ *   snapshots of the same tablet.
+ * Errors: also 8 when varlen_cap is smaller than the bytes to deliver;
+ *   *varlen_size then holds the size needed and the counters are filled as
+ *   for the row cap.
+ * With no string column projected it equals yb_gpu_snapshot_select, with
+ *   *varlen_size == 0.
+ * Memory: the per-row offsets, the scan scratch and the device heap are
+ *   snapshot-owned, grown on demand and counted in device_bytes.
+ * yb_gpu_snapshot_kernel_ms then also covers the string copy. */
+int yb_gpu_snapshot_select_var(ybg_snapshot_t *sn, const ybg_snapshot_select_t *q,
+                               uint64_t *datums, uint32_t *null_masks, uint64_t *row_ids,
+                               uint64_t cap, uint8_t *varlen, uint64_t varlen_cap,
+                               uint64_t *varlen_size, ybg_snapshot_select_result_t *out);
 /* Rows per compaction tile of the select kernels (tests derive edges from
  * it). */
 uint64_t ybg_snapshot_select_tile_rows(void);
@@ -594,7 +659,10 @@ int yb_gpu_snapshot_close(ybg_snapshot_t *sn);
  * handle, and answers that and later executes with the query kernel;
  * yb_gpu_scan_aggregate returns the same contents as the block path and
  * yb_gpu_scan_kernel_ms reports the query kernel's time. Ineligible handles
- * silently take the block path; unset or 0 changes nothing. */
+ * silently take the block path; unset or 0 changes nothing. The mode is
+ * unchanged by string staging: it keeps building numeric-only snapshots, so
+ * a handle with a string predicate or aggregate keeps taking the block
+ * path. */
 
 /* Returns 1 if a gfx950-class HIP device is visible. */
 int yb_gpu_available(void);

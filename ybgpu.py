@@ -489,6 +489,19 @@ class SnapshotInfo(C.Structure):
                 ("restart_ht_len", C.c_uint32)]
 
 
+class SnapshotBuildOpts(C.Structure):
+    """ybg_snapshot_build_opts_t."""
+    _fields_ = [("stage_strings", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class SnapshotStringInfo(C.Structure):
+    """ybg_snapshot_string_info_t."""
+    _fields_ = [("staged_string_value_cols", C.c_uint32),
+                ("staged_string_key_cols", C.c_uint32),
+                ("string_bytes", C.c_uint64 * MAX_COLS),
+                ("key_string_bytes", C.c_uint64 * MAX_KEYCOLS)]
+
+
 def snapshot_query(preds, aggs):
     """Pack predicate / aggregate lists into a SnapshotQuery. Counts over
     the ABI caps are passed through (the ABI answers them with code 9); only
@@ -503,25 +516,45 @@ def snapshot_query(preds, aggs):
     return q
 
 
-def stageable(schema, preds, aggs):
+def _string_in_list_ok(p):
+    """[u32 len][bytes] records that fill bytes_len exactly."""
+    raw = bytes(p.bytes[:p.bytes_len]) if p.bytes_len else b""
+    o = 0
+    while o + 4 <= len(raw):
+        o += 4 + int.from_bytes(raw[o:o + 4], "little")
+    return o == len(raw)
+
+
+def stageable(schema, preds, aggs, strings=False):
     """Can a columnar snapshot answer this query? Mirrors the ABI's code-9
     rule (yb_gpu_snapshot_query): GT..NE / IN / IN_RANGE predicates on
     numeric value or key columns, aggregates on numeric value columns,
-    indices in range, counts within the caps."""
+    indices in range, counts within the caps. strings=True: the rule of a
+    snapshot built with stage_strings — also GT..NE / IN on string value
+    and key columns and COUNT on a string value column."""
     if len(preds) > MAX_PREDS or len(aggs) > MAX_AGGS:
         return False
     nk = schema.num_hash_cols + schema.num_range_cols
     for p in preds:
         if p.op == PRED_IN_TUPLE or not PRED_GT <= p.op <= PRED_IN_RANGE:
             return False
+        is_str = False
         if p.is_key_col:
-            if not 0 <= p.col < nk or schema.key_types[p.col] == KT_STRING:
+            if not 0 <= p.col < nk:
                 return False
+            is_str = schema.key_types[p.col] == KT_STRING
         else:
             if not 0 <= p.col < schema.num_value_cols:
                 return False
-            if schema.value_cols[p.col].dtype == T_STRING:
+            is_str = schema.value_cols[p.col].dtype == T_STRING
+        if is_str:
+            if not strings or p.op == PRED_IN_RANGE:
                 return False
+            if p.bytes_len and not p.bytes:
+                return False
+            if p.op == PRED_IN and not _string_in_list_ok(p):
+                return False
+            continue
         if p.op == PRED_IN and (not p.bytes or p.bytes_len % 8):
             return False
         if p.op == PRED_IN_RANGE and (not p.bytes or not p.bytes_len
@@ -534,26 +567,41 @@ def stageable(schema, preds, aggs):
             continue
         if not 0 <= a.col < schema.num_value_cols:
             return False
-        if schema.value_cols[a.col].dtype == T_STRING:
+        if schema.value_cols[a.col].dtype == T_STRING and \
+                not (strings and a.op == AGG_COUNT):
             return False
     return True
 
 
-def sim_snapshot_query(spec, data, offsets, n_blocks, preds, aggs):
+def sim_snapshot_query(spec, data, offsets, n_blocks, preds, aggs,
+                       strings=False):
     """Host SIMULATOR of the columnar snapshot (ybg_sim_snapshot_query) —
     TEST INFRASTRUCTURE: builds the snapshot layout from the spec's read
     time and bounds (its predicates/aggregates are ignored) and runs the
-    device row loop (snap_device.h) over it for (preds, aggs)."""
+    device row loop (snap_device.h) over it for (preds, aggs).
+    strings=True builds it with stage_strings (ybg_sim_snapshot_query_ex).
+    A non-zero code raises RuntimeError carrying .code."""
     lib = product()
-    f = _sig(lib, "ybg_sim_snapshot_query", C.c_int,
-             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
-              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(SnapshotQuery),
-              C.POINTER(ScanResult)])
     q = snapshot_query(preds, aggs)
     res = ScanResult()
-    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), C.byref(res))
+    if strings:
+        f = _sig(lib, "ybg_sim_snapshot_query_ex", C.c_int,
+                 [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+                  C.POINTER(C.c_uint64), C.c_uint64,
+                  C.POINTER(SnapshotQuery), C.c_int, C.POINTER(ScanResult)])
+        rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), 1,
+               C.byref(res))
+    else:
+        f = _sig(lib, "ybg_sim_snapshot_query", C.c_int,
+                 [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+                  C.POINTER(C.c_uint64), C.c_uint64,
+                  C.POINTER(SnapshotQuery), C.POINTER(ScanResult)])
+        rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q),
+               C.byref(res))
     if rc != 0:
-        raise RuntimeError(f"ybg_sim_snapshot_query failed rc={rc}")
+        err = RuntimeError(f"ybg_sim_snapshot_query failed rc={rc}")
+        err.code = rc
+        raise err
     return res
 
 
@@ -624,28 +672,40 @@ def decode_snapshot_groups(res, keys, vals, cnts, aggs):
 
 def sim_snapshot_group_query(spec, data, offsets, n_blocks, preds, aggs,
                              group_col, group_is_key=False, expect_groups=0,
-                             cap=1 << 16):
+                             cap=1 << 16, strings=False):
     """Host SIMULATOR of the grouped snapshot query
     (ybg_sim_snapshot_group_query) — TEST INFRASTRUCTURE: the snapshot
     layout built as in sim_snapshot_query, then the device accumulate /
     flush / export code one simulated workgroup at a time. Returns
     (groups dict, (keys, vals, cnts) raw ctypes arrays, result struct);
-    raises RuntimeError carrying .code and .result on a non-zero code."""
+    raises RuntimeError carrying .code and .result on a non-zero code.
+    strings=True builds the snapshot with stage_strings
+    (ybg_sim_snapshot_group_query_ex)."""
     lib = product()
-    f = _sig(lib, "ybg_sim_snapshot_group_query", C.c_int,
+    f = _sig(lib, "ybg_sim_snapshot_group_query_ex", C.c_int,
              [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
               C.POINTER(C.c_uint64), C.c_uint64,
-              C.POINTER(SnapshotGroupQuery), C.POINTER(C.c_uint64),
+              C.POINTER(SnapshotGroupQuery), C.c_int, C.POINTER(C.c_uint64),
               C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64,
-              C.POINTER(SnapshotGroupResult)])
+              C.POINTER(SnapshotGroupResult)]) if strings else _sig(
+        lib, "ybg_sim_snapshot_group_query", C.c_int,
+        [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+         C.POINTER(C.c_uint64), C.c_uint64,
+         C.POINTER(SnapshotGroupQuery), C.POINTER(C.c_uint64),
+         C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64,
+         C.POINTER(SnapshotGroupResult)])
     q = snapshot_group_query(preds, aggs, group_col, group_is_key,
                              expect_groups)
     keys = (C.c_uint64 * max(cap, 1))()
     vals = (C.c_int64 * (max(cap, 1) * MAX_AGGS))()
     cnts = (C.c_uint64 * (max(cap, 1) * MAX_AGGS))()
     res = SnapshotGroupResult()
-    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), keys, vals,
-           cnts, cap, C.byref(res))
+    if strings:
+        rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), 1, keys,
+               vals, cnts, cap, C.byref(res))
+    else:
+        rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q), keys,
+               vals, cnts, cap, C.byref(res))
     if rc != 0:
         err = RuntimeError(f"ybg_sim_snapshot_group_query failed rc={rc}")
         err.code = rc
@@ -709,14 +769,35 @@ def snapshot_select_tile_rows():
     return _sig(product(), "ybg_snapshot_select_tile_rows", C.c_uint64, [])()
 
 
-def decode_snapshot_rows(res, datums, null_masks, num_cols, cols, cap):
+def select_string_cols(schema, cols):
+    """Per projected column: is it a string column of the schema?"""
+    out = []
+    for c in cols:
+        is_key, col = (c.is_key_col, c.col) if isinstance(c, SelectCol) else c
+        if is_key:
+            out.append(schema.key_types[col] == KT_STRING)
+        else:
+            out.append(schema.value_cols[col].dtype == T_STRING)
+    return out
+
+
+def decode_snapshot_rows(res, datums, null_masks, num_cols, cols, cap,
+                         varlen=None, string_cols=None):
     """Select output -> [(projected values..., None for NULL)], one tuple
     per delivered row in delivery order. cols: the (is_key_col, col) pairs
-    of the projection; cap: the capacity the arrays were passed with."""
+    of the projection; cap: the capacity the arrays were passed with.
+    string_cols (select_string_cols) marks the projected string columns:
+    their (len << 40) | offset datums are decoded to bytes from varlen."""
     cols = [(c.is_key_col, c.col) if isinstance(c, SelectCol) else c
             for c in cols]
     n = res.n_rows
     by_col = [datums[j * cap:j * cap + n] for j in range(num_cols)]
+    if string_cols and any(string_cols):
+        mask = (1 << 40) - 1
+        for j in range(num_cols):
+            if string_cols[j]:
+                by_col[j] = [bytes(varlen[(d & mask):(d & mask) + (d >> 40)])
+                             for d in by_col[j]]
     rows = list(zip(*by_col))
     for i, nm in enumerate(null_masks[:n]):
         if nm:
@@ -755,6 +836,43 @@ def sim_snapshot_select(spec, data, offsets, n_blocks, preds, cols, limit=0,
         err.result = res
         raise err
     return (datums, null_masks, row_ids), res
+
+
+def sim_snapshot_select_var(spec, data, offsets, n_blocks, preds, cols,
+                            limit=0, backward=False, row_lo=0, row_hi=None,
+                            cap=1 << 16, varlen_cap=1 << 20, strings=True):
+    """Host SIMULATOR of yb_gpu_snapshot_select_var
+    (ybg_sim_snapshot_select_var) — TEST INFRASTRUCTURE, as
+    sim_snapshot_select; the snapshot is built with stage_strings unless
+    strings=False. Returns ((datums, null_masks, row_ids, varlen,
+    varlen_size) raw arrays, result struct); raises RuntimeError carrying
+    .code, .result and .varlen_size on a non-zero code."""
+    lib = product()
+    f = _sig(lib, "ybg_sim_snapshot_select_var", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(SnapshotSelect),
+              C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8),
+              C.c_uint64, C.POINTER(C.c_uint64),
+              C.POINTER(SnapshotSelectResult)])
+    q = snapshot_select(preds, cols, limit, backward, row_lo, row_hi)
+    n = max(cap, 1)
+    datums = (C.c_uint64 * (n * max(1, min(len(cols), MAX_SELECT_COLS))))()
+    null_masks = (C.c_uint32 * n)()
+    row_ids = (C.c_uint64 * n)()
+    varlen = (C.c_uint8 * max(varlen_cap, 1))()
+    vsize = C.c_uint64()
+    res = SnapshotSelectResult()
+    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q),
+           1 if strings else 0, datums, null_masks, row_ids, cap, varlen,
+           varlen_cap, C.byref(vsize), C.byref(res))
+    if rc != 0:
+        err = RuntimeError(f"ybg_sim_snapshot_select_var failed rc={rc}")
+        err.code = rc
+        err.result = res
+        err.varlen_size = vsize.value
+        raise err
+    return (datums, null_masks, row_ids, varlen, vsize.value), res
 
 
 def sim_scan_fast(spec, data, offsets, n_blocks):

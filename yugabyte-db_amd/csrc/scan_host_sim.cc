@@ -530,9 +530,10 @@ int ybg_sim_emit(const ybg_scan_spec_t* spec, const uint8_t* data,
             &ho2, &wn, nullptr, &ec, rowbuf, lenbuf))
       return 6;
   }
-  if (overflow) return 8;
+  // set on overflow too: the counters then hold the sizes needed
   *n_rows_out = row_counter;
   *varlen_out = varlen_counter;
+  if (overflow) return 8;
   return 0;
 }
 
@@ -656,12 +657,18 @@ struct SimSnapshot {
   ybg_scan_result_t stats;
   std::vector<std::vector<uint64_t>> val, key;
   std::vector<uint32_t> nullmask;
+  // stage_strings: off / bytes / pfx per string column (SnapStrCol layout)
+  struct Str {
+    std::vector<uint64_t> off, pfx;
+    std::vector<uint8_t> bytes;
+  };
+  std::vector<Str> sval, skey;
   SnapCols cols;
 };
 
 int sim_snapshot_build(const ybg_scan_spec_t* spec, const uint8_t* data,
                        const uint64_t* offsets, uint64_t n_blocks,
-                       SimSnapshot* sn) {
+                       SimSnapshot* sn, bool stage_strings = false) {
   ybg_scan_spec_t bs = *spec;
   bs.num_preds = 0;
   bs.num_aggs = 0;
@@ -681,10 +688,23 @@ int sim_snapshot_build(const ybg_scan_spec_t* spec, const uint8_t* data,
       dat_aos(cap * (nc ? nc : 1));
   std::vector<uint32_t> null_aos(cap);
   uint64_t n = 0, vl = 0;
+  std::vector<uint8_t> heap;
+  if (stage_strings) {
+    // the device build's counting pass: a heap of capacity 0 takes no byte
+    // and leaves the exact size on the varlen counter
+    uint8_t none = 0;
+    rc = ybg_sim_emit(&bs, data, offsets, n_blocks, cap, sort_key.data(),
+                      key_aos.data(), dat_aos.data(), null_aos.data(), &none,
+                      0, &n, &vl);
+    if (rc && rc != 8) return rc;
+    if (n != stats.rows_scanned) return 8;
+    heap.assign(vl + 16, 0);
+  }
   // varlen heap absent: string datums are dropped, as in the device build
   rc = ybg_sim_emit(&bs, data, offsets, n_blocks, cap, sort_key.data(),
-                    key_aos.data(), dat_aos.data(), null_aos.data(), nullptr,
-                    0, &n, &vl);
+                    key_aos.data(), dat_aos.data(), null_aos.data(),
+                    stage_strings ? heap.data() : nullptr,
+                    stage_strings ? vl : 0, &n, &vl);
   if (rc) return rc;
   if (n != stats.rows_scanned) return 8;
   sn->n = n;
@@ -723,6 +743,36 @@ int sim_snapshot_build(const ybg_scan_spec_t* spec, const uint8_t* data,
     cols.nullable_cols |= nullmask[r] & nc_mask;
   }
   cols.nullmask = nullmask.data();
+  if (stage_strings) {
+    // k_snap_str_len / exclusive scan / k_snap_str_pack, serially
+    sn->sval.resize(nc);
+    sn->skey.resize(nk);
+    for (int pass = 0; pass < nk + nc; ++pass) {
+      const bool is_key = pass < nk;
+      const int c = is_key ? pass : pass - nk;
+      if (is_key ? sc.key_types[c] != YBG_KT_STRING
+                 : sc.value_cols[c].dtype != YBG_T_STRING)
+        continue;
+      const std::vector<uint64_t>& aos = is_key ? key_aos : dat_aos;
+      const int stride = is_key ? nk : nc;
+      SimSnapshot::Str& st = is_key ? sn->skey[c] : sn->sval[c];
+      st.off.assign(n + 1, 0);
+      st.pfx.assign(padded, 0);
+      for (uint64_t r = 0; r < n; ++r)
+        st.off[r + 1] =
+            st.off[r] + (aos[(uint64_t)perm[r] * stride + c] >> 40);
+      st.bytes.assign(st.off[n] + 16, 0);
+      for (uint64_t r = 0; r < n; ++r) {
+        const uint64_t d = aos[(uint64_t)perm[r] * stride + c];
+        const uint64_t len = d >> 40;
+        const uint8_t* src = heap.data() + (d & ((1ull << 40) - 1));
+        if (len) memcpy(st.bytes.data() + st.off[r], src, len);
+        st.pfx[r] = snap_str_prefix(src, len);
+      }
+      (is_key ? cols.skey[c] : cols.sval[c]) =
+          SnapStrCol{st.off.data(), st.bytes.data(), st.pfx.data()};
+    }
+  }
   return 0;
 }
 }  // namespace
@@ -733,12 +783,30 @@ extern "C" {
 // the snap_device.h row loop, sequentially. `query` is a
 // ybg_snapshot_query_t. Returns 9 for a query the ABI rejects (same
 // translation code).
+int ybg_sim_snapshot_query_ex(const ybg_scan_spec_t* spec,
+                              const uint8_t* data, const uint64_t* offsets,
+                              uint64_t n_blocks,
+                              const ybg_snapshot_query_t* query,
+                              int stage_strings, ybg_scan_result_t* out);
+
 int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
                            const uint64_t* offsets, uint64_t n_blocks,
                            const ybg_snapshot_query_t* query,
                            ybg_scan_result_t* out) {
+  return ybg_sim_snapshot_query_ex(spec, data, offsets, n_blocks, query, 0,
+                                   out);
+}
+
+// stage_strings: the snapshot is built as yb_gpu_snapshot_build_ex builds it
+// with that option.
+int ybg_sim_snapshot_query_ex(const ybg_scan_spec_t* spec,
+                              const uint8_t* data, const uint64_t* offsets,
+                              uint64_t n_blocks,
+                              const ybg_snapshot_query_t* query,
+                              int stage_strings, ybg_scan_result_t* out) {
   SimSnapshot snap;
-  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap,
+                              stage_strings != 0);
   if (rc) return rc;
   const ybg_schema_t& sc = spec->schema;
   const SnapCols& cols = snap.cols;
@@ -760,7 +828,7 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
   const uint64_t n_pairs = (n + kSnapVec - 1) / kSnapVec;
   auto run = [&](auto nulls_tag, auto gen_tag) {
     constexpr bool NULLS = decltype(nulls_tag)::value;
-    constexpr bool GEN = decltype(gen_tag)::value;
+    constexpr int GEN = decltype(gen_tag)::value;
     for (uint64_t pi = 0; pi < n_pairs; ++pi) {
       for (int k = 0; k < kSnapVec; ++k) {
         const uint64_t r = pi * kSnapVec + k;
@@ -769,17 +837,22 @@ int ybg_sim_snapshot_query(const ybg_scan_spec_t* spec, const uint8_t* data,
         for (int g = 0; g < q.num_aggs; ++g)
           if (q.aggs[g].col) av[g] = q.aggs[g].col[r];
         snap_row<YBG_MAX_PREDS, YBG_MAX_AGGS, NULLS, GEN>(
-            q, pv, av, NULLS ? q.nullmask[r] : 0u, r < n, &res.matched,
+            q, pv, av, NULLS ? q.nullmask[r] : 0u, r < n, r, &res.matched,
             res.agg_val, res.agg_cnt);
       }
     }
   };
+  using Fast = std::integral_constant<int, kSnapGenFast>;
+  using List = std::integral_constant<int, kSnapGenList>;
+  using Str = std::integral_constant<int, kSnapGenStr>;
   if (q.any_nullable) {
-    if (q.general) run(std::true_type{}, std::true_type{});
-    else run(std::true_type{}, std::false_type{});
+    if (q.general == kSnapGenStr) run(std::true_type{}, Str{});
+    else if (q.general) run(std::true_type{}, List{});
+    else run(std::true_type{}, Fast{});
   } else {
-    if (q.general) run(std::false_type{}, std::true_type{});
-    else run(std::false_type{}, std::false_type{});
+    if (q.general == kSnapGenStr) run(std::false_type{}, Str{});
+    else if (q.general) run(std::false_type{}, List{});
+    else run(std::false_type{}, Fast{});
   }
   snap_fill_result(res, n, stats.entries_seen, stats.restart_ht,
                    stats.restart_ht_len, query->num_aggs, query->aggs, out);
@@ -793,7 +866,7 @@ namespace {
 // k_snap_group_query, one simulated workgroup at a time: workgroup w of
 // snap_grid(n) walks the row pairs the device gives its 256 lanes
 // (grid-stride included) into its own local table, then flushes it.
-template <int NA, bool NULLS, bool GEN, bool LOCAL>
+template <int NA, bool NULLS, int GEN, bool LOCAL>
 void sim_group_rows(const SnapGroupQuery& gq, const GroupCtx& gc,
                     uint64_t* matched) {
   const SnapQuery& q = gq.q;
@@ -815,7 +888,7 @@ void sim_group_rows(const SnapGroupQuery& gq, const GroupCtx& gc,
             if (q.aggs[g].col) av[g] = q.aggs[g].col[r];
           snap_group_row<YBG_MAX_PREDS, NA, NULLS, GEN, LOCAL>(
               gq, pv, av, gq.grp_col[r], NULLS ? q.nullmask[r] : 0u, r < n,
-              matched, tab, gc);
+              r, matched, tab, gc);
         }
       }
     }
@@ -828,17 +901,20 @@ void sim_group_rows(const SnapGroupQuery& gq, const GroupCtx& gc,
 template <int NA>
 void sim_group_dispatch(const SnapGroupQuery& gq, const GroupCtx& gc,
                         bool local, uint64_t* matched) {
+  // the string instantiation stands in for the list one here: it runs the
+  // same pred_compare for a non-string slot
   const int v = (gq.q.any_nullable ? 4 : 0) | (gq.q.general ? 2 : 0) |
                 (local ? 1 : 0);
+  constexpr int G = kSnapGenStr;
   switch (v) {
-    case 0: sim_group_rows<NA, false, false, false>(gq, gc, matched); break;
-    case 1: sim_group_rows<NA, false, false, true>(gq, gc, matched); break;
-    case 2: sim_group_rows<NA, false, true, false>(gq, gc, matched); break;
-    case 3: sim_group_rows<NA, false, true, true>(gq, gc, matched); break;
-    case 4: sim_group_rows<NA, true, false, false>(gq, gc, matched); break;
-    case 5: sim_group_rows<NA, true, false, true>(gq, gc, matched); break;
-    case 6: sim_group_rows<NA, true, true, false>(gq, gc, matched); break;
-    default: sim_group_rows<NA, true, true, true>(gq, gc, matched); break;
+    case 0: sim_group_rows<NA, false, 0, false>(gq, gc, matched); break;
+    case 1: sim_group_rows<NA, false, 0, true>(gq, gc, matched); break;
+    case 2: sim_group_rows<NA, false, G, false>(gq, gc, matched); break;
+    case 3: sim_group_rows<NA, false, G, true>(gq, gc, matched); break;
+    case 4: sim_group_rows<NA, true, 0, false>(gq, gc, matched); break;
+    case 5: sim_group_rows<NA, true, 0, true>(gq, gc, matched); break;
+    case 6: sim_group_rows<NA, true, G, false>(gq, gc, matched); break;
+    default: sim_group_rows<NA, true, G, true>(gq, gc, matched); break;
   }
 }
 
@@ -850,6 +926,12 @@ extern "C" {
 // contract (codes 8 / 9 included) from the same translation, accumulate,
 // flush and export code, serially. The level is chosen from expect_groups
 // like the device dispatch chooses it.
+int ybg_sim_snapshot_group_query_ex(
+    const ybg_scan_spec_t* spec, const uint8_t* data, const uint64_t* offsets,
+    uint64_t n_blocks, const ybg_snapshot_group_query_t* query,
+    int stage_strings, uint64_t* keys, int64_t* vals, uint64_t* cnts,
+    uint64_t cap, ybg_snapshot_group_result_t* out);
+
 int ybg_sim_snapshot_group_query(const ybg_scan_spec_t* spec,
                                  const uint8_t* data, const uint64_t* offsets,
                                  uint64_t n_blocks,
@@ -857,9 +939,20 @@ int ybg_sim_snapshot_group_query(const ybg_scan_spec_t* spec,
                                  uint64_t* keys, int64_t* vals,
                                  uint64_t* cnts, uint64_t cap,
                                  ybg_snapshot_group_result_t* out) {
+  return ybg_sim_snapshot_group_query_ex(spec, data, offsets, n_blocks, query,
+                                         0, keys, vals, cnts, cap, out);
+}
+
+// stage_strings: as in ybg_sim_snapshot_query_ex.
+int ybg_sim_snapshot_group_query_ex(
+    const ybg_scan_spec_t* spec, const uint8_t* data, const uint64_t* offsets,
+    uint64_t n_blocks, const ybg_snapshot_group_query_t* query,
+    int stage_strings, uint64_t* keys, int64_t* vals, uint64_t* cnts,
+    uint64_t cap, ybg_snapshot_group_result_t* out) {
   memset(out, 0, sizeof(*out));
   SimSnapshot snap;
-  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap,
+                              stage_strings != 0);
   if (rc) return rc;
   const uint64_t n = snap.n;
   SnapGroupQuery gq;
@@ -939,7 +1032,7 @@ namespace {
 // k_snap_select_count, one simulated tile at a time: the lanes' two row
 // slots become the wave ballots, packed into the tile's bitmap words by the
 // shared code.
-template <bool NULLS, bool GEN>
+template <bool NULLS, int GEN>
 void sim_select_count(const SnapQuery& q, const SnapWindow& win,
                       uint64_t* bitmap, uint64_t* tile_cnt) {
   for (uint64_t t = 0; t < win.n_tiles; ++t) {
@@ -958,7 +1051,7 @@ void sim_select_count(const SnapQuery& q, const SnapWindow& win,
             for (int i = 0; i < q.num_preds; ++i) pv[i] = q.preds[i].col[r];
           const bool m = snap_pred_pass<YBG_MAX_PREDS, NULLS, GEN>(
               q, pv, (NULLS && ld) ? q.nullmask[r] : 0u,
-              r >= win.lo && r < win.hi);
+              r >= win.lo && r < win.hi, r);
           if (m) b[k] |= 1ull << lane;
         }
       }
@@ -981,15 +1074,38 @@ uint64_t ybg_sim_snapshot_select_tile_rows(void) { return kSnapTileRows; }
 // Select simulator: yb_gpu_snapshot_select's contract (codes 8 / 9
 // included) from the same translation, bit packing, rank, output index and
 // emit code, the tiles walked serially.
+int ybg_sim_snapshot_select_var(
+    const ybg_scan_spec_t* spec, const uint8_t* data, const uint64_t* offsets,
+    uint64_t n_blocks, const ybg_snapshot_select_t* query, int stage_strings,
+    uint64_t* datums, uint32_t* null_masks, uint64_t* row_ids, uint64_t cap,
+    uint8_t* varlen, uint64_t varlen_cap, uint64_t* varlen_size,
+    ybg_snapshot_select_result_t* out);
+
 int ybg_sim_snapshot_select(const ybg_scan_spec_t* spec, const uint8_t* data,
                             const uint64_t* offsets, uint64_t n_blocks,
                             const ybg_snapshot_select_t* query,
                             uint64_t* datums, uint32_t* null_masks,
                             uint64_t* row_ids, uint64_t cap,
                             ybg_snapshot_select_result_t* out) {
+  return ybg_sim_snapshot_select_var(spec, data, offsets, n_blocks, query, 0,
+                                     datums, null_masks, row_ids, cap,
+                                     nullptr, 0, nullptr, out);
+}
+
+// yb_gpu_snapshot_select_var's contract on a snapshot built with or without
+// stage_strings; varlen_size == nullptr: yb_gpu_snapshot_select's (a string
+// projection is refused).
+int ybg_sim_snapshot_select_var(
+    const ybg_scan_spec_t* spec, const uint8_t* data, const uint64_t* offsets,
+    uint64_t n_blocks, const ybg_snapshot_select_t* query, int stage_strings,
+    uint64_t* datums, uint32_t* null_masks, uint64_t* row_ids, uint64_t cap,
+    uint8_t* varlen, uint64_t varlen_cap, uint64_t* varlen_size,
+    ybg_snapshot_select_result_t* out) {
   memset(out, 0, sizeof(*out));
+  if (varlen_size) *varlen_size = 0;
   SimSnapshot snap;
-  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap);
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap,
+                              stage_strings != 0);
   if (rc) return rc;
   const uint64_t n_rows = snap.n;
   SnapQuery q;
@@ -997,7 +1113,7 @@ int ybg_sim_snapshot_select(const ybg_scan_spec_t* spec, const uint8_t* data,
   std::vector<uint8_t> aux;
   char err[192];
   rc = snap_build_select(spec->schema, &snap.cols, *query, n_rows, &aux, &q,
-                         &sel, err, sizeof(err));
+                         &sel, err, sizeof(err), varlen_size != nullptr);
   if (rc) return rc;
   q.aux = aux.data();
   out->entries_seen = snap.stats.entries_seen;
@@ -1016,15 +1132,16 @@ int ybg_sim_snapshot_select(const ybg_scan_spec_t* spec, const uint8_t* data,
   std::vector<uint64_t> tile_cnt(win.n_tiles);
   std::vector<uint32_t> tile_off(win.n_tiles);
   const int v = (q.any_nullable ? 2 : 0) | (q.general ? 1 : 0);
+  // as in sim_group_dispatch: the string instantiation covers the lists
   switch (v) {
-    case 0: sim_select_count<false, false>(q, win, bitmap.data(),
-                                           tile_cnt.data()); break;
-    case 1: sim_select_count<false, true>(q, win, bitmap.data(),
-                                          tile_cnt.data()); break;
-    case 2: sim_select_count<true, false>(q, win, bitmap.data(),
-                                          tile_cnt.data()); break;
-    default: sim_select_count<true, true>(q, win, bitmap.data(),
-                                          tile_cnt.data()); break;
+    case 0: sim_select_count<false, kSnapGenFast>(q, win, bitmap.data(),
+                                                  tile_cnt.data()); break;
+    case 1: sim_select_count<false, kSnapGenStr>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
+    case 2: sim_select_count<true, kSnapGenFast>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
+    default: sim_select_count<true, kSnapGenStr>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
   }
   // k_snap_select_scan, serially
   uint64_t total = 0;
@@ -1054,6 +1171,21 @@ int ybg_sim_snapshot_select(const ybg_scan_spec_t* spec, const uint8_t* data,
     for (uint32_t lane = 0; lane < (uint32_t)kSnapThreads; ++lane)
       snap_select_gather_pair(sel, so, h, bitmap.data() + tile * kSnapTileWords,
                               tile, off, lane * kSnapVec);
+  }
+  if (sel.num_str) {
+    // k_snap_select_strlen / exclusive scan / k_snap_select_strcopy
+    std::vector<uint64_t> row_off(n + 1, 0);
+    for (uint64_t i = 0; i < n; ++i)
+      row_off[i + 1] = row_off[i] + snap_select_row_strlen(sel, so, i);
+    *varlen_size = row_off[n];
+    if (row_off[n] > varlen_cap) {
+      snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+      out->done = 0;
+      out->resume_row = 0;
+      return 8;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+      snap_select_strcopy_row(sel, so, i, row_off[i], varlen);
   }
   snap_select_fill(lo, hi, h, sel.backward, row_ids[n - 1], row_ids[n - 1],
                    out);

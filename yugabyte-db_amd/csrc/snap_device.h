@@ -9,7 +9,9 @@
 // A snapshot is a DIFFERENT storage contract from "scan the reference's
 // SST block bytes" (DESIGN.md §4): rows visible at one read time, staged
 // once as one 8-byte datum per row per numeric column (the emit_row /
-// pred_cmp_fast bit pattern) plus one null-mask word per row.
+// pred_cmp_fast bit pattern) plus one null-mask word per row. A snapshot
+// built with stage_strings also holds every string column as an offsets
+// array, a byte heap and an 8-byte prefix column (SnapStrCol).
 #ifndef YBG_SNAP_DEVICE_H
 #define YBG_SNAP_DEVICE_H
 
@@ -71,6 +73,32 @@ struct SnapAgg {
   uint32_t null_m;      // null-mask bit of the operand (0: never NULL)
 };
 
+// One staged string column, in snapshot row order; every array is a pure
+// function of the rows.
+//   off[n_rows + 1]: byte offsets into `bytes`; row r's string is
+//     bytes[off[r], off[r + 1]). A NULL has length 0 (the null mask tells it
+//     from the empty string).
+//   bytes[off[n_rows] + 16]: the strings back to back, then 16 zero bytes.
+//   pfx[padded rows]: the string's first min(len, 8) bytes, big-endian (byte
+//     0 most significant), zero padded; 0 for a NULL. Padded and tail-zeroed
+//     like a numeric column, so a predicate streams it with the same 16-byte
+//     row-pair load.
+struct SnapStrCol {
+  const uint64_t* off;  // nullptr: column not staged
+  const uint8_t* bytes;
+  const uint64_t* pfx;
+};
+
+// Heap side of a string predicate slot (the slot's `col` is the pfx array).
+// The record lives in the query's aux buffer, 8-byte aligned, at the offset
+// the slot's pc.pad_ holds: SnapQuery keeps the layout the numeric-only
+// kernels were compiled against.
+struct SnapStrRef {
+  const uint64_t* off;
+  const uint8_t* bytes;
+  uint64_t rhs_pfx;  // compares: the rhs's padded prefix, computed on the host
+};
+
 // The query kernel's argument (POD, passed by value).
 struct SnapQuery {
   uint64_t n_rows;
@@ -78,9 +106,10 @@ struct SnapQuery {
   SnapPred preds[YBG_MAX_PREDS];
   SnapAgg aggs[YBG_MAX_AGGS];
   const uint32_t* nullmask;  // [padded rows]
-  const uint8_t* aux;        // IN / IN_RANGE lists
+  const uint8_t* aux;        // IN / IN_RANGE lists, string rhs bytes
   int32_t any_nullable;      // some referenced column holds a NULL
-  int32_t general;           // some predicate is IN / IN_RANGE
+  int32_t general;           // kSnapGenFast / List / Str: the compare code
+                             // the predicates need
 };
 
 // Staged column table of one snapshot (device pointers; host pointers in
@@ -90,20 +119,84 @@ struct SnapCols {
   const uint64_t* key[YBG_MAX_KEYCOLS];
   const uint32_t* nullmask;
   uint32_t nullable_cols;  // bit i: value col i has >= 1 NULL
+  SnapStrCol sval[YBG_MAX_COLS];    // staged string value / key columns
+  SnapStrCol skey[YBG_MAX_KEYCOLS];
 };
 
+// Padded prefix of a string (SnapStrCol.pfx).
+YBG_HD uint64_t snap_str_prefix(const uint8_t* s, uint64_t len) {
+  uint64_t p = 0;
+  for (uint64_t k = 0; k < 8; ++k)
+    p = (p << 8) | (k < len ? (uint64_t)s[k] : 0ull);
+  return p;
+}
+
+// A string predicate on row `row` of slot i; pfx: the row's prefix datum.
+//
+// Compares. memcmp order of two strings a, b is decided by their padded
+// prefixes P(a), P(b) whenever these differ, by a plain unsigned 64-bit
+// compare. Let k < 8 be the first byte where P(a) and P(b) differ. If
+// k < min(len a, len b), byte k is real in both strings and all earlier
+// bytes are equal, so memcmp decides on the same byte the same way. Otherwise
+// one string, say a, ends at or before k (both cannot: two pad bytes are
+// both 0 and would not differ). Bytes [0, k) are equal, and there a's pad
+// zeros face real zero bytes of b, so a is a proper prefix of b[0, k] and
+// memcmp puts a first; P(a)[k] is pad 0 and P(b)[k] differs from it, hence
+// is larger, so P(a) < P(b) as well. Equal prefixes decide nothing ("a" vs
+// "a\0"): only that tie reads the heap, through pred_compare's string
+// branch, so both paths keep one definition of the order.
+// IN always reads the heap (pred_compare's string-list branch).
+DEV bool snap_str_pred(const SnapQuery& q, int i, uint64_t pfx,
+                       uint64_t row) {
+  const PredC& pc = q.preds[i].pc;
+  const SnapStrRef& s = *reinterpret_cast<const SnapStrRef*>(q.aux + pc.pad_);
+#ifndef YBG_SNAP_STR_HEAP_ONLY  // measurement build: every compare is a tie
+  const uint32_t op = pc.opdt & 0xff;
+  if (op != YBG_PRED_IN && pfx != s.rhs_pfx) {
+    const bool lt = pfx < s.rhs_pfx;
+    switch (op) {
+      case YBG_PRED_GT: case YBG_PRED_GE: return !lt;
+      case YBG_PRED_LT: case YBG_PRED_LE: return lt;
+      case YBG_PRED_EQ: return false;
+      default: return true;
+    }
+  }
+#endif
+  const uint64_t o0 = s.off[row], o1 = s.off[row + 1];
+  return pred_compare(pc, 0, s.bytes + o0, (uint32_t)(o1 - o0), q.aux);
+}
+
+// Compare code of a kernel instantiation (template parameter GEN, picked
+// from SnapQuery.general): typed GT..NE compares only; + IN / IN_RANGE lists
+// through pred_compare; + string slots. The string branch has an
+// instantiation of its own so that numeric list queries run the code they
+// ran before it existed.
+constexpr int kSnapGenFast = 0, kSnapGenList = 1, kSnapGenStr = 2;
+
 // The predicate fold of one row, shared by the plain, grouped and select
-// paths: branch-free AND of every predicate slot below num_preds.
-template <int NP, bool NULLS, bool GEN>
+// paths: branch-free AND of every predicate slot below num_preds. row: the
+// row's snapshot position, used by string slots (kSnapGenStr only) for the
+// heap access; a row that is not `valid` never reaches the heap (its
+// position may lie past the offsets array).
+template <int NP, bool NULLS, int GEN>
 DEV bool snap_pred_pass(const SnapQuery& q, const uint64_t* pv, uint32_t nm,
-                        bool valid) {
+                        bool valid, uint64_t row) {
   bool pass = valid;
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     if (i >= q.num_preds) continue;
     const SnapPred& p = q.preds[i];
-    bool ok = GEN ? pred_compare(p.pc, pv[i], nullptr, 0, q.aux)
-                  : pred_cmp_fast(p.pc, pv[i]);
+    bool ok;
+    if constexpr (GEN == kSnapGenStr) {
+      if ((p.pc.opdt >> 8) == YBG_T_STRING)
+        ok = valid && snap_str_pred(q, i, pv[i], row);
+      else
+        ok = pred_compare(p.pc, pv[i], nullptr, 0, q.aux);
+    } else if constexpr (GEN == kSnapGenList) {
+      ok = pred_compare(p.pc, pv[i], nullptr, 0, q.aux);
+    } else {
+      ok = pred_cmp_fast(p.pc, pv[i]);
+    }
     if (NULLS) ok = ok & ((nm & p.null_m) == 0);
     pass = pass & ok;
   }
@@ -115,11 +208,11 @@ DEV bool snap_pred_pass(const SnapQuery& q, const uint64_t* pv, uint32_t nm,
 // exists (false for the padding row of an odd tail). NULL semantics are the
 // scan path's (eval_col / acc_row): a predicate on NULL fails; COUNT(col),
 // SUM, MIN, MAX skip NULL operands.
-template <int NP, int NA, bool NULLS, bool GEN>
+template <int NP, int NA, bool NULLS, int GEN>
 DEV void snap_row(const SnapQuery& q, const uint64_t* pv, const uint64_t* av,
-                  uint32_t nm, bool valid, uint64_t* matched,
+                  uint32_t nm, bool valid, uint64_t row, uint64_t* matched,
                   uint64_t* agg_val, uint64_t* agg_cnt) {
-  const bool pass = snap_pred_pass<NP, NULLS, GEN>(q, pv, nm, valid);
+  const bool pass = snap_pred_pass<NP, NULLS, GEN>(q, pv, nm, valid, row);
   *matched += pass ? 1 : 0;
 #pragma unroll
   for (int g = 0; g < NA; ++g) {
@@ -407,13 +500,13 @@ DEV void snap_local_flush_slot(const SnapQuery& q, SnapLocalTable<NA>* t,
 // One row of the grouped query: snap_row's predicate fold, then the row's
 // group datum / aggregate operands into `tab` (LOCAL) or the global table.
 // gv: the row's group-column datum.
-template <int NP, int NA, bool NULLS, bool GEN, bool LOCAL>
+template <int NP, int NA, bool NULLS, int GEN, bool LOCAL>
 DEV void snap_group_row(const SnapGroupQuery& gq, const uint64_t* pv,
                         const uint64_t* av, uint64_t gv, uint32_t nm,
-                        bool valid, uint64_t* matched,
+                        bool valid, uint64_t row, uint64_t* matched,
                         SnapLocalTable<NA>* tab, const GroupCtx& gc) {
   const SnapQuery& q = gq.q;
-  if (!snap_pred_pass<NP, NULLS, GEN>(q, pv, nm, valid)) return;
+  if (!snap_pred_pass<NP, NULLS, GEN>(q, pv, nm, valid, row)) return;
   *matched += 1;
   SnapGroupRow r;
   r.grp_datum = gv;
@@ -571,9 +664,9 @@ YBG_HD bool snap_select_out_index(const SnapSelectHdr& h, int backward,
 }
 
 struct SnapSelCol {
-  const uint64_t* col;  // staged column array
+  const uint64_t* col;  // staged column array; string column: its off array
   uint32_t null_m;      // null-mask bit of a value column, 0 for a key column
-  uint32_t pad_;
+  uint32_t is_str;      // 1: string column (select_var)
 };
 
 // The gather kernel's argument (POD, passed by value).
@@ -583,7 +676,8 @@ struct SnapSelect {
   SnapSelCol cols[YBG_MAX_SELECT_COLS];
   const uint32_t* nullmask;  // nullptr: no projected column holds a NULL
   uint32_t proj_mask;        // null-mask bits of the projected value columns
-  uint32_t pad_;
+  uint32_t num_str;          // projected string columns (repeats counted)
+  const uint8_t* str_bytes[YBG_MAX_SELECT_COLS];  // heap of string column j
 };
 
 struct SnapSelectOut {
@@ -595,6 +689,8 @@ struct SnapSelectOut {
 
 // One delivered row: position `pos` to output index `idx`. The null word is
 // masked to the projected value columns and a NULL's datum is written as 0.
+// A string column's datum is its length << 40 here; snap_select_strcopy_row
+// ORs the heap offset in.
 DEV void snap_select_emit(const SnapSelect& s, const SnapSelectOut& o,
                           uint64_t pos, uint64_t idx) {
   const uint32_t nm = s.nullmask ? (s.nullmask[pos] & s.proj_mask) : 0u;
@@ -602,8 +698,42 @@ DEV void snap_select_emit(const SnapSelect& s, const SnapSelectOut& o,
   o.null_masks[idx] = nm;
   for (int j = 0; j < s.num_cols; ++j) {
     const SnapSelCol& c = s.cols[j];
-    const uint64_t v = c.col[pos];
+    uint64_t v = c.col[pos];
+    if (c.is_str) v = (c.col[pos + 1] - v) << 40;
     o.datums[(uint64_t)j * o.cap + idx] = (nm & c.null_m) ? 0 : v;
+  }
+}
+
+// select_var, after the gather. The output heap is canonical: delivered rows
+// in delivery order, within a row the projected string columns in projection
+// order, bytes back to back.
+// Bytes delivered row `idx` puts on the heap.
+DEV uint64_t snap_select_row_strlen(const SnapSelect& s,
+                                    const SnapSelectOut& o, uint64_t idx) {
+  uint64_t t = 0;
+  for (int j = 0; j < s.num_cols; ++j)
+    if (s.cols[j].is_str) t += o.datums[(uint64_t)j * o.cap + idx] >> 40;
+  return t;
+}
+
+// Copy delivered row idx's strings to heap + row_off and complete their
+// datums to (len << 40) | offset (ybg_row_batch_t convention). A NULL keeps
+// datum 0 and takes no bytes.
+DEV void snap_select_strcopy_row(const SnapSelect& s, const SnapSelectOut& o,
+                                 uint64_t idx, uint64_t row_off,
+                                 uint8_t* heap) {
+  const uint64_t pos = o.row_ids[idx];
+  const uint32_t nm = o.null_masks[idx];
+  uint64_t at = row_off;
+  for (int j = 0; j < s.num_cols; ++j) {
+    const SnapSelCol& c = s.cols[j];
+    if (!c.is_str || (nm & c.null_m)) continue;
+    uint64_t* d = &o.datums[(uint64_t)j * o.cap + idx];
+    const uint64_t len = *d >> 40;
+    const uint8_t* src = s.str_bytes[j] + c.col[pos];
+    for (uint64_t k = 0; k < len; ++k) heap[at + k] = src[k];
+    *d |= at;
+    at += len;
   }
 }
 
@@ -639,6 +769,57 @@ DEV void snap_select_gather_pair(const SnapSelect& s, const SnapSelectOut& o,
 // cols == nullptr validates only (column pointers left null). IN / IN_RANGE
 // lists are appended to *aux; the caller uploads it and sets out->aux.
 // ---------------------------------------------------------------------------
+// One predicate on a staged string column -> its slot: its SnapStrRef, then
+// the rhs bytes (a compare) or the [u32 len][bytes] option records (IN) go
+// to *aux, the latter in the block path's PredC form. IN_RANGE is refused.
+inline int snap_build_str_pred(const ybg_pred_t& p, const SnapStrCol& str,
+                               int i, std::vector<uint8_t>* aux, SnapPred* sp,
+                               char* err, size_t err_cap) {
+  if (p.op == YBG_PRED_IN_RANGE) {
+    snprintf(err, err_cap,
+             "snapshot query: predicate %d: IN_RANGE is not supported on a "
+             "string column", i);
+    return 9;
+  }
+  aux->resize((aux->size() + 7) / 8 * 8, 0);
+  const uint64_t ref_off = aux->size();
+  const uint64_t off = ref_off + sizeof(SnapStrRef);
+  if ((p.bytes_len && !p.bytes) || p.bytes_len > 0xffffffffull ||
+      off + p.bytes_len > 0xffffffffull) {
+    snprintf(err, err_cap,
+             "snapshot query: predicate %d: malformed string operand", i);
+    return 9;
+  }
+  uint64_t head = p.bytes_len;  // compare: rhs length
+  if (p.op == YBG_PRED_IN) {
+    uint64_t o = 0, cnt = 0;
+    while (o + 4 <= p.bytes_len) {
+      uint32_t ol;
+      memcpy(&ol, p.bytes + o, 4);
+      o += 4 + (uint64_t)ol;
+      ++cnt;
+    }
+    if (o != p.bytes_len) {
+      snprintf(err, err_cap,
+               "snapshot query: predicate %d: malformed option list", i);
+      return 9;
+    }
+    head = cnt;
+  }
+  SnapStrRef ref;
+  ref.off = str.off;
+  ref.bytes = str.bytes;
+  ref.rhs_pfx =
+      p.op == YBG_PRED_IN ? 0 : snap_str_prefix(p.bytes, p.bytes_len);
+  const uint8_t* rb = reinterpret_cast<const uint8_t*>(&ref);
+  aux->insert(aux->end(), rb, rb + sizeof(ref));
+  if (p.bytes_len) aux->insert(aux->end(), p.bytes, p.bytes + p.bytes_len);
+  sp->pc.opdt = (uint32_t)p.op | ((uint32_t)YBG_T_STRING << 8);
+  sp->pc.datum = (head << 32) | off;
+  sp->pc.pad_ = (uint32_t)ref_off;
+  return 0;
+}
+
 inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
                             int32_t num_preds, const ybg_pred_t* preds,
                             int32_t num_aggs, const ybg_agg_t* aggs,
@@ -682,15 +863,26 @@ inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
                  i, p.col);
         return 9;
       }
+      const SnapStrCol* str = nullptr;
       if (sc.key_types[p.col] == YBG_KT_STRING) {
-        snprintf(err, err_cap,
-                 "snapshot query: predicate %d: string key column %d is not "
-                 "staged", i, p.col);
-        return 9;
+        if (!cols || !cols->skey[p.col].off) {
+          snprintf(err, err_cap,
+                   "snapshot query: predicate %d: string key column %d is not "
+                   "staged", i, p.col);
+          return 9;
+        }
+        str = &cols->skey[p.col];
       }
-      dt = YBG_T_INT64;  // key datums are sign-extended (key_col_value)
-      if (cols) sp.col = cols->key[p.col];
+      dt = str ? YBG_T_STRING
+               : YBG_T_INT64;  // key datums are sign-extended (key_col_value)
+      if (cols) sp.col = str ? str->pfx : cols->key[p.col];
       sp.null_m = 0;
+      if (str) {
+        int rc = snap_build_str_pred(p, *str, i, aux, &sp, err, err_cap);
+        if (rc) return rc;
+        out->general = kSnapGenStr;
+        continue;
+      }
     } else {
       if (p.col < 0 || p.col >= sc.num_value_cols) {
         snprintf(err, err_cap,
@@ -699,15 +891,23 @@ inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
         return 9;
       }
       dt = sc.value_cols[p.col].dtype;
-      if (dt == YBG_T_STRING) {
+      if (dt == YBG_T_STRING && (!cols || !cols->sval[p.col].off)) {
         snprintf(err, err_cap,
                  "snapshot query: predicate %d: string column %d is not "
                  "staged", i, p.col);
         return 9;
       }
-      if (cols) sp.col = cols->val[p.col];
+      if (cols)
+        sp.col = dt == YBG_T_STRING ? cols->sval[p.col].pfx : cols->val[p.col];
       sp.null_m = 1u << p.col;
       if (nullable & sp.null_m) out->any_nullable = 1;
+      if (dt == YBG_T_STRING) {
+        int rc = snap_build_str_pred(p, cols->sval[p.col], i, aux, &sp, err,
+                                     err_cap);
+        if (rc) return rc;
+        out->general = kSnapGenStr;
+        continue;
+      }
     }
     sp.pc.opdt = (uint32_t)p.op | ((uint32_t)dt << 8);
     sp.pc.datum = p.datum;
@@ -728,7 +928,7 @@ inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
       }
       aux->insert(aux->end(), p.bytes, p.bytes + p.bytes_len);
       sp.pc.datum = ((p.bytes_len / rec) << 32) | off;
-      out->general = 1;
+      if (out->general < kSnapGenList) out->general = kSnapGenList;
     }
   }
   for (int g = 0; g < num_aggs; ++g) {
@@ -748,10 +948,18 @@ inline int snap_build_query(const ybg_schema_t& sc, const SnapCols* cols,
       return 9;
     }
     if (sc.value_cols[a.col].dtype == YBG_T_STRING) {
-      snprintf(err, err_cap,
-               "snapshot query: aggregate %d: string column %d is not staged",
-               g, a.col);
-      return 9;
+      if (!cols || !cols->sval[a.col].off) {
+        snprintf(err, err_cap,
+                 "snapshot query: aggregate %d: string column %d is not "
+                 "staged", g, a.col);
+        return 9;
+      }
+      if (a.op != YBG_AGG_COUNT) {
+        snprintf(err, err_cap,
+                 "snapshot query: aggregate %d: only COUNT is supported on "
+                 "string column %d", g, a.col);
+        return 9;
+      }
     }
     sa.null_m = 1u << a.col;
     if (nullable & sa.null_m) out->any_nullable = 1;
@@ -821,10 +1029,13 @@ inline int snap_build_group_query(const ybg_schema_t& sc,
 // ABI select -> SnapQuery (predicates, zero aggregates) + SnapSelect (the
 // projection: any staged value or key column, 1 .. YBG_MAX_SELECT_COLS
 // entries, repeats allowed).
+// allow_strings (yb_gpu_snapshot_select_var): staged string columns may be
+// projected too.
 inline int snap_build_select(const ybg_schema_t& sc, const SnapCols* cols,
                              const ybg_snapshot_select_t& sq, uint64_t n_rows,
                              std::vector<uint8_t>* aux, SnapQuery* out_q,
-                             SnapSelect* out, char* err, size_t err_cap) {
+                             SnapSelect* out, char* err, size_t err_cap,
+                             bool allow_strings = false) {
   memset(out, 0, sizeof(*out));
   int rc = snap_build_query(sc, cols, sq.num_preds, sq.preds, 0, nullptr,
                             n_rows, aux, out_q, err, err_cap);
@@ -855,12 +1066,25 @@ inline int snap_build_select(const ybg_schema_t& sc, const SnapCols* cols,
         return 9;
       }
       if (sc.key_types[c.col] == YBG_KT_STRING) {
-        snprintf(err, err_cap,
-                 "snapshot select: column %d: string key column %d is not "
-                 "staged", j, c.col);
-        return 9;
+        if (!cols || !cols->skey[c.col].off) {
+          snprintf(err, err_cap,
+                   "snapshot select: column %d: string key column %d is not "
+                   "staged", j, c.col);
+          return 9;
+        }
+        if (!allow_strings) {
+          snprintf(err, err_cap,
+                   "snapshot select: column %d: string key column %d needs "
+                   "yb_gpu_snapshot_select_var", j, c.col);
+          return 9;
+        }
+        o.col = cols->skey[c.col].off;
+        o.is_str = 1;
+        out->str_bytes[j] = cols->skey[c.col].bytes;
+        ++out->num_str;
+      } else if (cols) {
+        o.col = cols->key[c.col];
       }
-      if (cols) o.col = cols->key[c.col];
     } else {
       if (c.col < 0 || c.col >= sc.num_value_cols) {
         snprintf(err, err_cap,
@@ -869,12 +1093,25 @@ inline int snap_build_select(const ybg_schema_t& sc, const SnapCols* cols,
         return 9;
       }
       if (sc.value_cols[c.col].dtype == YBG_T_STRING) {
-        snprintf(err, err_cap,
-                 "snapshot select: column %d: string column %d is not staged",
-                 j, c.col);
-        return 9;
+        if (!cols || !cols->sval[c.col].off) {
+          snprintf(err, err_cap,
+                   "snapshot select: column %d: string column %d is not "
+                   "staged", j, c.col);
+          return 9;
+        }
+        if (!allow_strings) {
+          snprintf(err, err_cap,
+                   "snapshot select: column %d: string column %d needs "
+                   "yb_gpu_snapshot_select_var", j, c.col);
+          return 9;
+        }
+        o.col = cols->sval[c.col].off;
+        o.is_str = 1;
+        out->str_bytes[j] = cols->sval[c.col].bytes;
+        ++out->num_str;
+      } else if (cols) {
+        o.col = cols->val[c.col];
       }
-      if (cols) o.col = cols->val[c.col];
       o.null_m = 1u << c.col;
       out->proj_mask |= o.null_m;
     }

@@ -24,12 +24,21 @@
 //    key order as an ordered stream compaction in three launches (per-tile
 //    match bitmap + counts, one-workgroup prefix sum, rank and gather of the
 //    projected columns); no workgroup waits on another.
+//  * strings (yb_gpu_snapshot_build_ex with stage_strings): k_emit fills a
+//    temporary heap sized by a counting emit pass; per string column
+//    k_snap_str_len / rocprim exclusive scan / k_snap_str_pack turn it into
+//    row-ordered offsets, bytes and an 8-byte prefix column. A string
+//    predicate streams the prefix column like a numeric one and reads the
+//    heap only on a prefix tie (snap_str_pred); select_var adds
+//    k_snap_select_strlen / exclusive scan / k_snap_select_strcopy behind the
+//    gather, launch boundaries only.
 //  The grid is a pure function of n_rows, so together with the sorted
 //  build, results (double SUM included) are bit-identical across queries
 //  and across separately built snapshots of the same tablet.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <cstdlib>
 #include <cstring>
@@ -62,9 +71,10 @@ typedef unsigned int snap_u32x2 __attribute__((ext_vector_type(2)));
 // Query kernel. NP / NA: compile-time caps of the unrolled predicate /
 // aggregate loops (slots past num_preds / num_aggs are skipped with uniform
 // branches and load nothing). NULLS = false never touches the null-mask
-// array. GEN routes compares through pred_compare (IN / IN_RANGE lists).
+// array. GEN (kSnapGenFast / List / Str) picks the compare code: typed
+// compares, + pred_compare (IN / IN_RANGE lists), + string slots.
 // ---------------------------------------------------------------------------
-template <int NP, int NA, bool NULLS, bool GEN>
+template <int NP, int NA, bool NULLS, int GEN>
 __global__ __launch_bounds__(kSnapThreads) void k_snap_query(
     SnapQuery q, uint64_t* __restrict__ partials) {
   const uint64_t n_pairs = (q.n_rows + kSnapVec - 1) / kSnapVec;
@@ -102,9 +112,9 @@ __global__ __launch_bounds__(kSnapThreads) void k_snap_query(
 #pragma unroll
     for (int g = 0; g < NA; ++g) { a0[g] = av[g].x; a1[g] = av[g].y; }
     // ascending row order per lane; the odd tail's padding row is masked
-    snap_row<NP, NA, NULLS, GEN>(q, p0, a0, nm.x, true, &matched, agg_val,
-                                 agg_cnt);
-    snap_row<NP, NA, NULLS, GEN>(q, p1, a1, nm.y, r0 + 1 < q.n_rows,
+    snap_row<NP, NA, NULLS, GEN>(q, p0, a0, nm.x, true, r0, &matched,
+                                 agg_val, agg_cnt);
+    snap_row<NP, NA, NULLS, GEN>(q, p1, a1, nm.y, r0 + 1 < q.n_rows, r0 + 1,
                                  &matched, agg_val, agg_cnt);
   }
 
@@ -186,7 +196,7 @@ __global__ __launch_bounds__(256) void k_snap_reduce(
 // after the row loop; otherwise straight to the global table. Both barriers
 // sit outside the grid-stride loop. rows_matched: one integer add per wave.
 // ---------------------------------------------------------------------------
-template <int NP, int NA, bool NULLS, bool GEN, bool LOCAL>
+template <int NP, int NA, bool NULLS, int GEN, bool LOCAL>
 __global__ __launch_bounds__(kSnapThreads) void k_snap_group_query(
     SnapGroupQuery gq, GroupCtx gc, unsigned long long* __restrict__ matched_out) {
   const SnapQuery& q = gq.q;
@@ -231,10 +241,10 @@ __global__ __launch_bounds__(kSnapThreads) void k_snap_group_query(
     for (int g = 0; g < NA; ++g) { a0[g] = av[g].x; a1[g] = av[g].y; }
     // the odd tail's padding row is masked
     snap_group_row<NP, NA, NULLS, GEN, LOCAL>(gq, p0, a0, gv.x, nm.x, true,
-                                              &matched, tab, gc);
+                                              r0, &matched, tab, gc);
     snap_group_row<NP, NA, NULLS, GEN, LOCAL>(gq, p1, a1, gv.y, nm.y,
-                                              r0 + 1 < q.n_rows, &matched,
-                                              tab, gc);
+                                              r0 + 1 < q.n_rows, r0 + 1,
+                                              &matched, tab, gc);
   }
 
   if constexpr (LOCAL) {
@@ -332,7 +342,7 @@ __global__ __launch_bounds__(256) void k_snap_group_export(
 // outside [lo, hi) are masked out of the fold. Each wave packs its two
 // ballots into two bitmap words and writes its match count into its own
 // 16-bit lane of the tile's count word: no LDS, no barrier.
-template <int NP, bool NULLS, bool GEN>
+template <int NP, bool NULLS, int GEN>
 __global__ __launch_bounds__(kSnapThreads) void k_snap_select_count(
     SnapQuery q, SnapWindow win, unsigned long long* __restrict__ bitmap,
     unsigned long long* __restrict__ tile_cnt) {
@@ -355,9 +365,9 @@ __global__ __launch_bounds__(kSnapThreads) void k_snap_select_count(
 #pragma unroll
     for (int i = 0; i < NP; ++i) { p0[i] = pv[i].x; p1[i] = pv[i].y; }
     const bool m0 = snap_pred_pass<NP, NULLS, GEN>(
-        q, p0, nm.x, r0 >= win.lo && r0 < win.hi);
+        q, p0, nm.x, r0 >= win.lo && r0 < win.hi, r0);
     const bool m1 = snap_pred_pass<NP, NULLS, GEN>(
-        q, p1, nm.y, r0 + 1 >= win.lo && r0 + 1 < win.hi);
+        q, p1, nm.y, r0 + 1 >= win.lo && r0 + 1 < win.hi, r0 + 1);
     const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
     if (lane == 0) {
       uint64_t w[2];
@@ -511,6 +521,61 @@ __global__ __launch_bounds__(256) void k_snap_transpose(
   if ((threadIdx.x & 63) == 0 && nm) atomicOr(nullable_out, nm);
 }
 
+// String staging (stage_strings builds), one column per launch, after the
+// sort. A string column's AoS datum is k_emit's (len << 40) | emit-heap
+// offset, 0 for a NULL: column `idx` of `stride` in key_aos / dat_aos.
+constexpr uint64_t kSnapStrOffMask = (1ull << 40) - 1;
+
+// len[r] = length of output row r's string, len[n_rows] = 0 (so the
+// exclusive scan over n_rows + 1 items ends in the total).
+__global__ __launch_bounds__(256) void k_snap_str_len(
+    const uint64_t* __restrict__ aos, int stride, int idx,
+    const uint32_t* __restrict__ perm, uint64_t n_rows,
+    uint64_t* __restrict__ len) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r < n_rows)
+    len[r] = aos[(uint64_t)perm[r] * stride + idx] >> 40;
+  else if (r == n_rows)
+    len[r] = 0;
+}
+
+// Output row r: its bytes from the emit heap to bytes + off[r], its padded
+// prefix to pfx[r]. off[r] + len <= off[n_rows], the size of `bytes`.
+__global__ __launch_bounds__(256) void k_snap_str_pack(
+    const uint64_t* __restrict__ aos, int stride, int idx,
+    const uint32_t* __restrict__ perm, uint64_t n_rows,
+    const uint8_t* __restrict__ heap, const uint64_t* __restrict__ off,
+    uint8_t* __restrict__ bytes, uint64_t* __restrict__ pfx) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const uint64_t d = aos[(uint64_t)perm[r] * stride + idx];
+  const uint64_t len = d >> 40;
+  const uint8_t* src = heap + (d & kSnapStrOffMask);
+  uint8_t* dst = bytes + off[r];
+  for (uint64_t k = 0; k < len; ++k) dst[k] = src[k];
+  pfx[r] = snap_str_prefix(src, len);
+}
+
+// select_var: per delivered row, the bytes its projected strings take.
+// len[n] = 0, as in k_snap_str_len.
+__global__ __launch_bounds__(256) void k_snap_select_strlen(
+    SnapSelect s, SnapSelectOut o, uint64_t n, uint64_t* __restrict__ len) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n)
+    len[i] = snap_select_row_strlen(s, o, i);
+  else if (i == n)
+    len[i] = 0;
+}
+
+// select_var: delivered row i's strings to heap + row_off[i], offsets into
+// the datums.
+__global__ __launch_bounds__(256) void k_snap_select_strcopy(
+    SnapSelect s, SnapSelectOut o, uint64_t n,
+    const uint64_t* __restrict__ row_off, uint8_t* __restrict__ heap) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) snap_select_strcopy_row(s, o, i, row_off[i], heap);
+}
+
 // temporaries of one build: freed on every exit path
 struct DevTmp {
   std::vector<void*> ptrs;
@@ -576,6 +641,25 @@ struct ybg_snapshot {
   uint32_t* d_sel_nulls = nullptr;              // [sel_cap]
   uint64_t* d_sel_datums = nullptr;             // [sel_cols * sel_cap]
   uint64_t sel_cap = 0, sel_cols = 0;
+  // staged string columns (stage_strings builds; SnapStrCol layout)
+  uint32_t str_value_cols = 0, str_key_cols = 0;
+  uint64_t* d_sval_off[YBG_MAX_COLS] = {nullptr};
+  uint8_t* d_sval_bytes[YBG_MAX_COLS] = {nullptr};
+  uint64_t* d_sval_pfx[YBG_MAX_COLS] = {nullptr};
+  uint64_t sval_total[YBG_MAX_COLS] = {0};
+  uint64_t* d_skey_off[YBG_MAX_KEYCOLS] = {nullptr};
+  uint8_t* d_skey_bytes[YBG_MAX_KEYCOLS] = {nullptr};
+  uint64_t* d_skey_pfx[YBG_MAX_KEYCOLS] = {nullptr};
+  uint64_t skey_total[YBG_MAX_KEYCOLS] = {0};
+  // select_var: per-row byte counts / offsets ([sel_str_cap + 1]), the scan's
+  // temporary storage and the output heap, all grown on demand
+  uint64_t* d_sel_strlen = nullptr;
+  uint64_t* d_sel_stroff = nullptr;
+  uint64_t sel_str_cap = 0;
+  void* d_sel_scan = nullptr;
+  size_t sel_scan_bytes = 0;
+  uint8_t* d_sel_heap = nullptr;
+  uint64_t sel_heap_cap = 0;
 };
 
 namespace {
@@ -600,6 +684,20 @@ void snap_free(ybg_snapshot* sn) {
                     sn->d_sel_datums};
   for (void* p : select)
     if (p) HIP_WARN(hipFree(p));
+  for (int c = 0; c < YBG_MAX_COLS; ++c) {
+    void* str[] = {sn->d_sval_off[c], sn->d_sval_bytes[c], sn->d_sval_pfx[c]};
+    for (void* p : str)
+      if (p) HIP_WARN(hipFree(p));
+  }
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c) {
+    void* str[] = {sn->d_skey_off[c], sn->d_skey_bytes[c], sn->d_skey_pfx[c]};
+    for (void* p : str)
+      if (p) HIP_WARN(hipFree(p));
+  }
+  void* select_var[] = {sn->d_sel_strlen, sn->d_sel_stroff, sn->d_sel_scan,
+                        sn->d_sel_heap};
+  for (void* p : select_var)
+    if (p) HIP_WARN(hipFree(p));
   if (sn->ev_s0) HIP_WARN(hipEventDestroy(sn->ev_s0));
   if (sn->ev_s1) HIP_WARN(hipEventDestroy(sn->ev_s1));
   if (sn->ev_q0) HIP_WARN(hipEventDestroy(sn->ev_q0));
@@ -615,6 +713,14 @@ SnapCols snap_cols(const ybg_snapshot* sn) {
   for (int c = 0; c < YBG_MAX_KEYCOLS; ++c) cols.key[c] = sn->d_key[c];
   cols.nullmask = sn->d_nullmask;
   cols.nullable_cols = sn->nullable_cols;
+  for (int c = 0; c < YBG_MAX_COLS; ++c)
+    if ((sn->str_value_cols >> c) & 1)
+      cols.sval[c] = SnapStrCol{sn->d_sval_off[c], sn->d_sval_bytes[c],
+                                sn->d_sval_pfx[c]};
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c)
+    if ((sn->str_key_cols >> c) & 1)
+      cols.skey[c] = SnapStrCol{sn->d_skey_off[c], sn->d_skey_bytes[c],
+                                sn->d_skey_pfx[c]};
   return cols;
 }
 
@@ -639,10 +745,10 @@ template <int NP, int NA>
 void snap_launch_fast(const SnapQuery& q, int grid, hipStream_t st,
                       uint64_t* partials) {
   if (q.any_nullable)
-    hipLaunchKernelGGL((k_snap_query<NP, NA, true, false>), dim3(grid),
+    hipLaunchKernelGGL((k_snap_query<NP, NA, true, kSnapGenFast>), dim3(grid),
                        dim3(kSnapThreads), 0, st, q, partials);
   else
-    hipLaunchKernelGGL((k_snap_query<NP, NA, false, false>), dim3(grid),
+    hipLaunchKernelGGL((k_snap_query<NP, NA, false, kSnapGenFast>), dim3(grid),
                        dim3(kSnapThreads), 0, st, q, partials);
 }
 
@@ -672,14 +778,23 @@ int snap_launch(ybg_snapshot* sn, int32_t num_preds, const ybg_pred_t* preds,
   if (int arc = snap_upload_aux(sn, &q)) return arc;
   const int grid = (int)snap_grid(sn->n_rows);
   HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
-  if (q.general) {
+  if (q.general == kSnapGenStr) {
     if (q.any_nullable)
-      hipLaunchKernelGGL((k_snap_query<8, 8, true, true>), dim3(grid),
+      hipLaunchKernelGGL((k_snap_query<8, 8, true, kSnapGenStr>), dim3(grid),
                          dim3(kSnapThreads), 0, sn->stream, q,
                          sn->d_partials);
     else
-      hipLaunchKernelGGL((k_snap_query<8, 8, false, true>), dim3(grid),
+      hipLaunchKernelGGL((k_snap_query<8, 8, false, kSnapGenStr>), dim3(grid),
                          dim3(kSnapThreads), 0, sn->stream, q,
+                         sn->d_partials);
+  } else if (q.general) {
+    if (q.any_nullable)
+      hipLaunchKernelGGL((k_snap_query<8, 8, true, kSnapGenList>), dim3(grid),
+                         dim3(kSnapThreads), 0, sn->stream, q,
+                         sn->d_partials);
+    else
+      hipLaunchKernelGGL((k_snap_query<8, 8, false, kSnapGenList>),
+                         dim3(grid), dim3(kSnapThreads), 0, sn->stream, q,
                          sn->d_partials);
   } else {
     const int np = q.num_preds <= 4 ? 4 : 8;
@@ -742,7 +857,7 @@ struct GroupLaunch {
   bool local;
 };
 
-template <int NP, int NA, bool GEN>
+template <int NP, int NA, int GEN>
 void snap_group_launch_na(const GroupLaunch& l) {
   const dim3 g(l.grid), b(kSnapThreads);
   const bool nulls = l.gq->q.any_nullable;
@@ -765,7 +880,7 @@ void snap_group_launch_na(const GroupLaunch& l) {
 
 // NA follows num_aggs for the IN / IN_RANGE kernels too, so the local slot
 // count is a function of num_aggs alone (ybg_snapshot_group_local_slots).
-template <int NP, bool GEN>
+template <int NP, int GEN>
 void snap_group_launch_np(const GroupLaunch& l) {
   switch (snap_group_na(l.gq->q.num_aggs)) {
     case 2: snap_group_launch_na<NP, 2, GEN>(l); break;
@@ -843,9 +958,10 @@ int snap_group_query(ybg_snapshot* sn, const ybg_snapshot_group_query_t* gqa,
                      sn->stream, ops, gc);
   GroupLaunch l{&gq, &gc, sn->d_gctr + 2, (int)snap_grid(sn->n_rows),
                 sn->stream, local};
-  if (gq.q.general) snap_group_launch_np<8, true>(l);
-  else if (gq.q.num_preds <= 4) snap_group_launch_np<4, false>(l);
-  else snap_group_launch_np<8, false>(l);
+  if (gq.q.general == kSnapGenStr) snap_group_launch_np<8, kSnapGenStr>(l);
+  else if (gq.q.general) snap_group_launch_np<8, kSnapGenList>(l);
+  else if (gq.q.num_preds <= 4) snap_group_launch_np<4, kSnapGenFast>(l);
+  else snap_group_launch_np<8, kSnapGenFast>(l);
   const int cgrid = (int)((gc.cap + kCompactThreads - 1) / kCompactThreads < 256
                               ? (gc.cap + kCompactThreads - 1) / kCompactThreads
                               : 256);
@@ -933,7 +1049,7 @@ int snap_group_query(ybg_snapshot* sn, const ybg_snapshot_group_query_t* gqa,
 
 // ---- select -----------------------------------------------------------------
 
-template <int NP, bool GEN>
+template <int NP, int GEN>
 void snap_select_launch_count(const SnapQuery& q, const SnapWindow& win,
                               int grid, hipStream_t st,
                               unsigned long long* bitmap,
@@ -988,9 +1104,58 @@ int snap_select_ensure_out(ybg_snapshot* sn, uint64_t n, uint64_t ncols) {
   return 0;
 }
 
+// select_var scratch for n delivered rows: the per-row byte counts and
+// offsets (n + 1 entries each) and the scan's temporary storage.
+int snap_select_ensure_str(ybg_snapshot* sn, uint64_t n, size_t scan_need) {
+  int rc = 0;
+  if (n > sn->sel_str_cap) {
+    void* old[] = {sn->d_sel_strlen, sn->d_sel_stroff};
+    for (void* p : old)
+      if (p) HIP_WARN(hipFree(p));
+    sn->d_sel_strlen = nullptr;
+    sn->d_sel_stroff = nullptr;
+    if (sn->sel_str_cap) sn->device_bytes -= 2 * (sn->sel_str_cap + 1) * 8;
+    sn->sel_str_cap = 0;
+    uint64_t want = 1024;
+    while (want < n) want <<= 1;
+    if ((rc = snap_group_alloc(sn, &sn->d_sel_strlen, (want + 1) * 8)))
+      return rc;
+    if ((rc = snap_group_alloc(sn, &sn->d_sel_stroff, (want + 1) * 8)))
+      return rc;
+    sn->sel_str_cap = want;
+  }
+  if (scan_need > sn->sel_scan_bytes) {
+    if (sn->d_sel_scan) HIP_WARN(hipFree(sn->d_sel_scan));
+    sn->d_sel_scan = nullptr;
+    sn->device_bytes -= sn->sel_scan_bytes;
+    sn->sel_scan_bytes = 0;
+    if ((rc = snap_group_alloc(sn, &sn->d_sel_scan, scan_need))) return rc;
+    sn->sel_scan_bytes = scan_need;
+  }
+  return 0;
+}
+
+// The select_var output heap, at least `bytes` long.
+int snap_select_ensure_heap(ybg_snapshot* sn, uint64_t bytes) {
+  if (bytes <= sn->sel_heap_cap) return 0;
+  if (sn->d_sel_heap) HIP_WARN(hipFree(sn->d_sel_heap));
+  sn->d_sel_heap = nullptr;
+  sn->device_bytes -= sn->sel_heap_cap;
+  sn->sel_heap_cap = 0;
+  uint64_t want = 1 << 16;
+  while (want < bytes) want <<= 1;
+  int rc = snap_group_alloc(sn, &sn->d_sel_heap, want);
+  if (rc) return rc;
+  sn->sel_heap_cap = want;
+  return 0;
+}
+
+// varlen_size == nullptr: yb_gpu_snapshot_select (no string projection);
+// otherwise yb_gpu_snapshot_select_var.
 int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
                 uint64_t* datums, uint32_t* null_masks, uint64_t* row_ids,
-                uint64_t cap, ybg_snapshot_select_result_t* out) {
+                uint64_t cap, uint8_t* varlen, uint64_t varlen_cap,
+                uint64_t* varlen_size, ybg_snapshot_select_result_t* out) {
   memset(out, 0, sizeof(*out));
   const SnapCols cols = snap_cols(sn);
   SnapQuery q;
@@ -1000,7 +1165,8 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
   if (sn->pending) HIP_TRY(hipStreamSynchronize(sn->stream));
   sn->aux_host.clear();
   int rc = snap_build_select(sn->schema, &cols, *sq, sn->n_rows,
-                             &sn->aux_host, &q, &sel, err, sizeof(err));
+                             &sn->aux_host, &q, &sel, err, sizeof(err),
+                             varlen_size != nullptr);
   if (rc) return set_err(rc, err);
   out->entries_seen = sn->entries_seen;
   memcpy(out->restart_ht, sn->restart_ht, sn->restart_len);
@@ -1020,15 +1186,21 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
   const int grid =
       (int)(win.n_tiles < kSnapMaxGrid ? win.n_tiles : kSnapMaxGrid);
   HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
-  if (q.general)
-    snap_select_launch_count<8, true>(q, win, grid, sn->stream,
-                                      sn->d_sel_bitmap, sn->d_sel_cnt);
+  if (q.general == kSnapGenStr)
+    snap_select_launch_count<8, kSnapGenStr>(q, win, grid, sn->stream,
+                                             sn->d_sel_bitmap, sn->d_sel_cnt);
+  else if (q.general)
+    snap_select_launch_count<8, kSnapGenList>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
   else if (q.num_preds <= 4)
-    snap_select_launch_count<4, false>(q, win, grid, sn->stream,
-                                       sn->d_sel_bitmap, sn->d_sel_cnt);
+    snap_select_launch_count<4, kSnapGenFast>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
   else
-    snap_select_launch_count<8, false>(q, win, grid, sn->stream,
-                                       sn->d_sel_bitmap, sn->d_sel_cnt);
+    snap_select_launch_count<8, kSnapGenFast>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
   hipLaunchKernelGGL(k_snap_select_scan, dim3(1), dim3(kSnapScanThreads), 0,
                      sn->stream, sn->d_sel_cnt, sn->d_sel_off, win.n_tiles,
                      snap_select_tile_slots(win.n_tiles), sq->row_limit,
@@ -1061,7 +1233,44 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
   hipLaunchKernelGGL(k_snap_select_gather, dim3(grid), dim3(kSnapThreads), 0,
                      sn->stream, sel, so, win, sn->d_sel_bitmap,
                      sn->d_sel_cnt, sn->d_sel_off, sn->d_sel_hdr);
+  uint64_t heap_bytes = 0;
+  if (sel.num_str) {
+    // per-row byte counts -> exclusive scan -> row offsets; the total sizes
+    // the heap, its copy and the varlen_cap check
+    const int sgrid = (int)((n + 1 + 255) / 256);
+    size_t need = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, need, sn->d_sel_strlen,
+                                    sn->d_sel_stroff, (uint64_t)0,
+                                    (size_t)(n + 1),
+                                    rocprim::plus<uint64_t>(), sn->stream));
+    if ((rc = snap_select_ensure_str(sn, n, need))) return rc;
+    hipLaunchKernelGGL(k_snap_select_strlen, dim3(sgrid), dim3(256), 0,
+                       sn->stream, sel, so, n, sn->d_sel_strlen);
+    HIP_TRY(rocprim::exclusive_scan(sn->d_sel_scan, need, sn->d_sel_strlen,
+                                    sn->d_sel_stroff, (uint64_t)0,
+                                    (size_t)(n + 1),
+                                    rocprim::plus<uint64_t>(), sn->stream));
+    HIP_TRY(hipMemcpyAsync(&heap_bytes, sn->d_sel_stroff + n, 8,
+                           hipMemcpyDeviceToHost, sn->stream));
+    HIP_TRY(hipStreamSynchronize(sn->stream));
+    *varlen_size = heap_bytes;
+    if (heap_bytes > varlen_cap) {
+      snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
+      out->done = 0;
+      out->resume_row = 0;
+      return set_err(8, "snapshot select: " + std::to_string(heap_bytes) +
+                            " string bytes exceed the varlen capacity " +
+                            std::to_string(varlen_cap));
+    }
+    if ((rc = snap_select_ensure_heap(sn, heap_bytes))) return rc;
+    hipLaunchKernelGGL(k_snap_select_strcopy, dim3(sgrid), dim3(256), 0,
+                       sn->stream, sel, so, n, sn->d_sel_stroff,
+                       sn->d_sel_heap);
+  }
   HIP_TRY(hipEventRecord(sn->ev_s1, sn->stream));
+  if (heap_bytes)
+    HIP_TRY(hipMemcpyAsync(varlen, sn->d_sel_heap, heap_bytes,
+                           hipMemcpyDeviceToHost, sn->stream));
   HIP_TRY(hipMemcpyAsync(row_ids, sn->d_sel_rowids, n * 8,
                          hipMemcpyDeviceToHost, sn->stream));
   HIP_TRY(hipMemcpyAsync(null_masks, sn->d_sel_nulls, n * 4,
@@ -1106,8 +1315,35 @@ int stage_finish(ybg_snapshot_t* snap, const ybg_scan_spec_t& spec,
 
 }  // namespace ybgint
 
+namespace {
+
+// Storage of one staged string column holding `total` bytes: off / bytes /
+// pfx (SnapStrCol), the bytes' 16-byte slack and the pfx tail zeroed on st.
+int snap_str_alloc(ybg_snapshot* sn, bool is_key, int c, uint64_t n,
+                   uint64_t total, hipStream_t st) {
+  uint64_t** off = is_key ? &sn->d_skey_off[c] : &sn->d_sval_off[c];
+  uint8_t** bytes = is_key ? &sn->d_skey_bytes[c] : &sn->d_sval_bytes[c];
+  uint64_t** pfx = is_key ? &sn->d_skey_pfx[c] : &sn->d_sval_pfx[c];
+  const uint64_t padded = snap_padded_rows(n);
+  if (!*off) {
+    HIP_TRY(hipMalloc(off, (n + 1) * 8));
+    sn->device_bytes += (n + 1) * 8;
+    if (n == 0) HIP_TRY(hipMemsetAsync(*off, 0, 8, st));
+  }
+  HIP_TRY(hipMalloc(bytes, total + 16));
+  sn->device_bytes += total + 16;
+  HIP_TRY(hipMemsetAsync(*bytes + total, 0, 16, st));
+  HIP_TRY(hipMalloc(pfx, padded * 8));
+  sn->device_bytes += padded * 8;
+  HIP_TRY(hipMemsetAsync(*pfx + n, 0, (padded - n) * 8, st));
+  (is_key ? sn->skey_total[c] : sn->sval_total[c]) = total;
+  return 0;
+}
+
+}  // namespace
+
 int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
-                           bool allow_option_pruned) {
+                           bool allow_option_pruned, bool stage_strings) {
   *out = nullptr;
   ybgint::ScanView v = ybgint::scan_view(s);
   if (!v.fed && !v.bloom_rejected)
@@ -1132,6 +1368,14 @@ int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
       sn->staged_value_cols |= 1u << c;
   for (int c = 0; c < nk; ++c)
     if (sc.key_types[c] != YBG_KT_STRING) sn->staged_key_cols |= 1u << c;
+  if (stage_strings) {
+    for (int c = 0; c < nc; ++c)
+      if (sc.value_cols[c].dtype == YBG_T_STRING)
+        sn->str_value_cols |= 1u << c;
+    for (int c = 0; c < nk; ++c)
+      if (sc.key_types[c] == YBG_KT_STRING) sn->str_key_cols |= 1u << c;
+  }
+  const bool any_str = (sn->str_value_cols | sn->str_key_cols) != 0;
   // every exit below the allocations frees the half-built snapshot
   struct Guard {
     ybg_snapshot* sn;
@@ -1212,6 +1456,31 @@ int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
       ec.nk = nk;
       ec.nc = nc;
       unsigned long long ctr[4];
+      uint8_t* t_heap = nullptr;
+      if (any_str) {
+        // The emit heap is sized exactly by a counting pass: with a heap of
+        // capacity 0 emit_row still reserves every string's bytes on the
+        // varlen counter (a key string its escaped length, an upper bound
+        // of what it writes), finds each reservation over the capacity and
+        // writes nothing. The counter's final value is the sum of all
+        // reservations, so in the real pass below, under the same DevSpec
+        // and ownership flags, every reservation ends inside the heap.
+        // (The blocks' byte total is no bound: prefix-compressed key
+        // strings expand.) The rows this pass writes are overwritten.
+        HIP_TRY(tmp.alloc(&t_heap, 1));
+        ec.varlen = t_heap;
+        rc = ybgint::scan_emit_pass(s, d_aux, ec, t_ctr, ctr);
+        if (rc) return rc;
+        if (ctr[3])
+          return set_err(6, "corrupt entries encountered during scan");
+        if (ctr[0] != n) return set_err(8, "snapshot row capacity exceeded");
+        const uint64_t heap_bytes = ctr[1];
+        if (heap_bytes > kSnapStrOffMask)
+          return set_err(8, "snapshot string capacity (2^40 bytes) exceeded");
+        HIP_TRY(tmp.alloc(&t_heap, heap_bytes + 16));
+        ec.varlen = t_heap;
+        ec.varlen_cap = heap_bytes;
+      }
       rc = ybgint::scan_emit_pass(s, d_aux, ec, t_ctr, ctr);
       if (rc) return rc;
       if (ctr[3])
@@ -1279,6 +1548,53 @@ int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
       HIP_TRY(hipMemsetAsync(t_nullable, 0, 4, v.stream));
       hipLaunchKernelGGL(k_snap_transpose, dim3(rgrid), dim3(256), 0,
                          v.stream, x, t_perm, n, t_nullable);
+      if (any_str) {
+        // per string column: lengths following perm -> exclusive scan ->
+        // off; the total sizes the bytes; pack copies the bytes and writes
+        // the prefixes
+        uint64_t* t_len = nullptr;
+        HIP_TRY(tmp.alloc(&t_len, (n + 1) * 8));
+        const int lgrid = (int)((n + 1 + 255) / 256);
+        void* t_scan = nullptr;
+        size_t scan_bytes = 0;
+        for (int pass = 0; pass < nk + nc; ++pass) {
+          const bool is_key = pass < nk;
+          const int c = is_key ? pass : pass - nk;
+          if (!(((is_key ? sn->str_key_cols : sn->str_value_cols) >> c) & 1))
+            continue;
+          const uint64_t* aos = is_key ? t_key : t_dat;
+          const int stride = is_key ? nk : nc;
+          uint64_t** off = is_key ? &sn->d_skey_off[c] : &sn->d_sval_off[c];
+          HIP_TRY(hipMalloc(off, (n + 1) * 8));
+          sn->device_bytes += (n + 1) * 8;
+          hipLaunchKernelGGL(k_snap_str_len, dim3(lgrid), dim3(256), 0,
+                             v.stream, aos, stride, c, t_perm, n, t_len);
+          size_t need = 0;
+          HIP_TRY(rocprim::exclusive_scan(nullptr, need, t_len, *off,
+                                          (uint64_t)0, (size_t)(n + 1),
+                                          rocprim::plus<uint64_t>(),
+                                          v.stream));
+          if (need > scan_bytes) {
+            HIP_TRY(tmp.alloc(&t_scan, need));
+            scan_bytes = need;
+          }
+          HIP_TRY(rocprim::exclusive_scan(t_scan, need, t_len, *off,
+                                          (uint64_t)0, (size_t)(n + 1),
+                                          rocprim::plus<uint64_t>(),
+                                          v.stream));
+          uint64_t total = 0;
+          HIP_TRY(hipMemcpyAsync(&total, *off + n, 8, hipMemcpyDeviceToHost,
+                                 v.stream));
+          HIP_TRY(hipStreamSynchronize(v.stream));
+          if ((rc = snap_str_alloc(sn, is_key, c, n, total, v.stream)))
+            return rc;
+          hipLaunchKernelGGL(
+              k_snap_str_pack, dim3(rgrid), dim3(256), 0, v.stream, aos,
+              stride, c, t_perm, n, t_heap, *off,
+              is_key ? sn->d_skey_bytes[c] : sn->d_sval_bytes[c],
+              is_key ? sn->d_skey_pfx[c] : sn->d_sval_pfx[c]);
+        }
+      }
       HIP_TRY(hipEventRecord(ev_b1, v.stream));
       HIP_TRY(hipMemcpyAsync(&sn->nullable_cols, t_nullable, 4,
                              hipMemcpyDeviceToHost, v.stream));
@@ -1297,6 +1613,20 @@ int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
     sn->build_ms = ms;
     // tmp's destructor frees the AoS temporaries here
   }
+  if (sn->n_rows == 0 && any_str) {
+    // no rows: off = {0}, an empty heap and a zero prefix pad, so string
+    // queries are accepted and answer zero rows
+    int rc = 0;
+    for (int c = 0; c < nc; ++c)
+      if (((sn->str_value_cols >> c) & 1) &&
+          (rc = snap_str_alloc(sn, false, c, 0, 0, sn->stream)))
+        return rc;
+    for (int c = 0; c < nk; ++c)
+      if (((sn->str_key_cols >> c) & 1) &&
+          (rc = snap_str_alloc(sn, true, c, 0, 0, sn->stream)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(sn->stream));
+  }
   guard.sn = nullptr;
   *out = sn;
   return 0;
@@ -1304,8 +1634,26 @@ int ybgint::snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
 
 extern "C" {
 
+int yb_gpu_snapshot_build_ex(ybg_scan_t* s,
+                             const ybg_snapshot_build_opts_t* opts,
+                             ybg_snapshot_t** out) {
+  return ybgint::snapshot_build(s, out, false, opts && opts->stage_strings);
+}
+
 int yb_gpu_snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out) {
-  return ybgint::snapshot_build(s, out, false);
+  return yb_gpu_snapshot_build_ex(s, nullptr, out);
+}
+
+int yb_gpu_snapshot_string_info(ybg_snapshot_t* sn,
+                                ybg_snapshot_string_info_t* out) {
+  memset(out, 0, sizeof(*out));
+  out->staged_string_value_cols = sn->str_value_cols;
+  out->staged_string_key_cols = sn->str_key_cols;
+  for (int c = 0; c < YBG_MAX_COLS; ++c)
+    out->string_bytes[c] = sn->sval_total[c];
+  for (int c = 0; c < YBG_MAX_KEYCOLS; ++c)
+    out->key_string_bytes[c] = sn->skey_total[c];
+  return 0;
 }
 
 int yb_gpu_snapshot_info(ybg_snapshot_t* sn, ybg_snapshot_info_t* out) {
@@ -1340,7 +1688,20 @@ int yb_gpu_snapshot_select(ybg_snapshot_t* sn, const ybg_snapshot_select_t* q,
                            uint64_t* datums, uint32_t* null_masks,
                            uint64_t* row_ids, uint64_t cap,
                            ybg_snapshot_select_result_t* out) {
-  return snap_select(sn, q, datums, null_masks, row_ids, cap, out);
+  return snap_select(sn, q, datums, null_masks, row_ids, cap, nullptr, 0,
+                     nullptr, out);
+}
+
+int yb_gpu_snapshot_select_var(ybg_snapshot_t* sn,
+                               const ybg_snapshot_select_t* q,
+                               uint64_t* datums, uint32_t* null_masks,
+                               uint64_t* row_ids, uint64_t cap,
+                               uint8_t* varlen, uint64_t varlen_cap,
+                               uint64_t* varlen_size,
+                               ybg_snapshot_select_result_t* out) {
+  *varlen_size = 0;
+  return snap_select(sn, q, datums, null_masks, row_ids, cap, varlen,
+                     varlen_cap, varlen_size, out);
 }
 
 uint64_t ybg_snapshot_select_tile_rows(void) { return kSnapTileRows; }

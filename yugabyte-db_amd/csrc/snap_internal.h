@@ -56,8 +56,10 @@ int scan_emit_pass(ybg_scan_t* s, const uint8_t* d_aux, ybgdev::EmitCtx ec,
 // fed block set was pruned by its own option predicate — only sound when
 // every query will carry that predicate (the YBG_STAGE mode); the public
 // entry point refuses such handles.
+// stage_strings: stage the string value / key columns too
+// (yb_gpu_snapshot_build_ex); the YBG_STAGE mode never sets it.
 int snapshot_build(ybg_scan_t* s, ybg_snapshot_t** out,
-                   bool allow_option_pruned);
+                   bool allow_option_pruned, bool stage_strings = false);
 
 // YBG_STAGE=1 transparent mode (scan_gpu.hip calls into snap_gpu.hip).
 // can the spec's predicates/aggregates be answered from a snapshot?

@@ -12,11 +12,17 @@
 // — unlimited, limited, backward and odd-window variants — and is
 // cross-checked against the block-path emit simulator (ybg_sim_emit, rows
 // ordered by sort_key).
+// A string tablet (string value column with NULLs and shared 8-byte prefixes,
+// string range-key column holding \0) built with stage_strings then runs a
+// string EQ, a tie-breaking LT, a key IN and a select_var (forward, backward
+// with a limit, varlen capacity one byte short), cross-checked against the
+// block-path simulator and the rows the driver wrote.
 // TEST INFRASTRUCTURE; not linked into the product library.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "../../include/yb_gpu_scan.h"
@@ -46,6 +52,16 @@ extern "C" int ybg_sim_emit(const ybg_scan_spec_t*, const uint8_t*,
                             const uint64_t*, uint64_t, uint64_t, uint64_t*,
                             uint64_t*, uint64_t*, uint32_t*, uint8_t*,
                             uint64_t, uint64_t*, uint64_t*);
+
+extern "C" int ybg_sim_snapshot_query_ex(const ybg_scan_spec_t*,
+                                         const uint8_t*, const uint64_t*,
+                                         uint64_t,
+                                         const ybg_snapshot_query_t*, int,
+                                         ybg_scan_result_t*);
+extern "C" int ybg_sim_snapshot_select_var(
+    const ybg_scan_spec_t*, const uint8_t*, const uint64_t*, uint64_t,
+    const ybg_snapshot_select_t*, int, uint64_t*, uint32_t*, uint64_t*,
+    uint64_t, uint8_t*, uint64_t, uint64_t*, ybg_snapshot_select_result_t*);
 
 namespace {
 
@@ -297,6 +313,179 @@ int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
   return bad;
 }
 
+// Row r of the string tablet: value NULL on every 5th row, else
+// "prefix-8" + r's decimal digits cut to r % 14 bytes (under, at and over
+// the 8-byte prefix, many ties on it); range key "k\0" + r % 7.
+std::string str_value(uint64_t r) {
+  char buf[40];
+  snprintf(buf, sizeof(buf), "prefix-8%06llu", (unsigned long long)r);
+  return std::string(buf).substr(0, r % 14);
+}
+std::string str_key(uint64_t r) {
+  std::string k("k\0", 2);
+  return k + (char)('0' + r % 7);
+}
+
+int check_strings(uint64_t n) {
+  ybg_schema_t schema;
+  memset(&schema, 0, sizeof(schema));
+  schema.has_hash = 1;
+  schema.num_hash_cols = 1;
+  schema.num_range_cols = 1;
+  schema.key_types[0] = YBG_KT_INT64;
+  schema.key_types[1] = YBG_KT_STRING;
+  schema.num_value_cols = 2;
+  schema.value_cols[0] = {10, YBG_T_STRING, 1};
+  schema.value_cols[1] = {11, YBG_T_INT64, 1};
+  ybg_builder_t* b =
+      ybg_builder_create(&schema, YBG_ENC_THREE_SHARED_PARTS, 4096, 16);
+  std::vector<std::string> vals(n), keys(n);
+  for (uint64_t r = 0; r < n; ++r) {
+    vals[r] = str_value(r);
+    keys[r] = str_key(r);
+    ybg_key_t k;
+    memset(&k, 0, sizeof(k));
+    k.hash = (uint16_t)(r / 64);
+    k.datums[0] = r;
+    k.strs[1] = (const uint8_t*)keys[r].data();
+    k.str_lens[1] = keys[r].size();
+    ybg_rowvals_t v;
+    memset(&v, 0, sizeof(v));
+    v.null[0] = r % 5 == 4 ? 1 : 0;
+    v.strs[0] = (const uint8_t*)vals[r].data();
+    v.str_lens[0] = vals[r].size();
+    v.datums[1] = r;
+    if (ybg_builder_add_packed_row(b, &k, (1000 + r) << 12, 0,
+                                   (1ull << 50) + r, 2, &v))
+      return 1;
+  }
+  const uint8_t* data;
+  const uint64_t* offsets;
+  uint64_t n_blocks, total, n_entries;
+  if (ybg_builder_finish(b, &data, &offsets, &n_blocks, &total, &n_entries))
+    return 1;
+  ybg_scan_spec_t spec;
+  memset(&spec, 0, sizeof(spec));
+  spec.schema = schema;
+  spec.kv_format = YBG_ENC_THREE_SHARED_PARTS;
+  ybg_read_time_init(&spec.read_time, 1000000ull << 12, 1000000ull << 12,
+                     1000000ull << 12);
+
+  int bad = 0;
+  // EQ on a value some row holds; LT whose rhs ties most rows on the prefix;
+  // IN on the key column with a hit, a miss and the empty string
+  const std::string eq = str_value(n > 12 ? 12 : 0);
+  const std::string lt = "prefix-8000003";
+  std::string in;
+  for (const std::string& o :
+       {std::string("k\0" "3", 3), std::string("absent"), std::string()}) {
+    const uint32_t l = (uint32_t)o.size();
+    in.append((const char*)&l, 4);
+    in += o;
+  }
+  ybg_snapshot_query_t qs[3];
+  memset(qs, 0, sizeof(qs));
+  for (ybg_snapshot_query_t& q : qs) {
+    q.num_preds = 1;
+    q.num_aggs = 3;
+    q.aggs[0] = {YBG_AGG_COUNT_STAR, 0};
+    q.aggs[1] = {YBG_AGG_COUNT, 0};
+    q.aggs[2] = {YBG_AGG_SUM_INT64, 1};
+  }
+  qs[0].preds[0] = {0, 0, YBG_PRED_EQ, 0, (const uint8_t*)eq.data(),
+                    eq.size()};
+  qs[1].preds[0] = {0, 0, YBG_PRED_LT, 0, (const uint8_t*)lt.data(),
+                    lt.size()};
+  qs[2].preds[0] = {1, 1, YBG_PRED_IN, 0, (const uint8_t*)in.data(),
+                    in.size()};
+  for (const ybg_snapshot_query_t& q : qs) {
+    ybg_scan_result_t snap, blk, plain;
+    int rc = ybg_sim_snapshot_query_ex(&spec, data, offsets, n_blocks, &q, 1,
+                                       &snap);
+    // a snapshot built without strings keeps refusing the query
+    int rc9 = ybg_sim_snapshot_query(&spec, data, offsets, n_blocks, &q,
+                                     &plain);
+    ybg_scan_spec_t bs = spec;
+    bs.num_preds = q.num_preds;
+    memcpy(bs.preds, q.preds, sizeof(bs.preds));
+    bs.num_aggs = q.num_aggs;
+    memcpy(bs.aggs, q.aggs, sizeof(bs.aggs));
+    int rc2 = ybg_sim_scan(&bs, data, offsets, n_blocks, &blk);
+    int lbad = rc || rc2 || rc9 != 9 || snap.rows_matched != blk.rows_matched ||
+               snap.rows_scanned != blk.rows_scanned;
+    for (int g = 0; g < q.num_aggs && !lbad; ++g)
+      lbad = snap.aggs[g].is_null != blk.aggs[g].is_null ||
+             (!blk.aggs[g].is_null &&
+              snap.aggs[g].value_i64 != blk.aggs[g].value_i64);
+    printf("strings n=%llu op=%d: matched=%llu %s\n", (unsigned long long)n,
+           q.preds[0].op, (unsigned long long)snap.rows_matched,
+           lbad ? "MISMATCH" : "ok");
+    bad |= lbad;
+  }
+
+  // select_var: value string, int64, key string, the value string again
+  ybg_snapshot_select_t sq;
+  memset(&sq, 0, sizeof(sq));
+  sq.num_cols = 4;
+  sq.cols[0] = {0, 0};
+  sq.cols[1] = {0, 1};
+  sq.cols[2] = {1, 1};
+  sq.cols[3] = {0, 0};
+  sq.row_hi = UINT64_MAX;
+  const uint64_t cap = n + 1;
+  std::vector<uint64_t> datums(cap * 4), ids(cap);
+  std::vector<uint32_t> nms(cap);
+  for (int variant = 0; variant < 2; ++variant) {
+    sq.backward = variant;
+    sq.row_limit = variant ? 9 : 0;
+    std::vector<uint64_t> want;  // positions in delivery order
+    for (uint64_t i = 0; i < n; ++i) want.push_back(variant ? n - 1 - i : i);
+    if (sq.row_limit && want.size() > sq.row_limit) want.resize(sq.row_limit);
+    std::string heap_want;
+    for (uint64_t r : want) {
+      if (r % 5 != 4) heap_want += vals[r];
+      heap_want += keys[r];
+      if (r % 5 != 4) heap_want += vals[r];
+    }
+    std::vector<uint8_t> heap(heap_want.size() + 1);
+    uint64_t vsize = 0;
+    ybg_snapshot_select_result_t res;
+    int rc = ybg_sim_snapshot_select_var(
+        &spec, data, offsets, n_blocks, &sq, 1, datums.data(), nms.data(),
+        ids.data(), cap, heap.data(), heap_want.size(), &vsize, &res);
+    int lbad = rc || res.n_rows != want.size() ||
+               vsize != heap_want.size() ||
+               memcmp(heap.data(), heap_want.data(), heap_want.size()) != 0;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < want.size() && !lbad; ++i) {
+      const uint64_t r = want[i];
+      const bool null = r % 5 == 4;
+      const uint64_t vl = null ? 0 : vals[r].size();
+      const uint64_t d0 = null ? 0 : (vl << 40) | at;
+      const uint64_t d2 = ((uint64_t)keys[r].size() << 40) | (at + vl);
+      const uint64_t d3 =
+          null ? 0 : (vl << 40) | (at + vl + keys[r].size());
+      lbad = ids[i] != r || nms[i] != (null ? 1u : 0u) || datums[i] != d0 ||
+             datums[cap + i] != r || datums[2 * cap + i] != d2 ||
+             datums[3 * cap + i] != d3;
+      at += 2 * vl + keys[r].size();
+    }
+    // one byte short: code 8 and the size needed
+    if (!lbad && !heap_want.empty()) {
+      rc = ybg_sim_snapshot_select_var(
+          &spec, data, offsets, n_blocks, &sq, 1, datums.data(), nms.data(),
+          ids.data(), cap, heap.data(), heap_want.size() - 1, &vsize, &res);
+      lbad = rc != 8 || vsize != heap_want.size();
+    }
+    printf("strings n=%llu select_var backward=%d: rows=%zu heap=%zu %s\n",
+           (unsigned long long)n, variant, want.size(), heap_want.size(),
+           lbad ? "MISMATCH" : "ok");
+    bad |= lbad;
+  }
+  ybg_builder_destroy(b);
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -347,6 +536,9 @@ int main() {
     bad |= check_one(schema, n, 1000000, qg, true);
   }
   bad |= check_one(schema, 65, 500, q, true);  // read time before every write
+  for (uint64_t n : {(uint64_t)1, (uint64_t)2, tile - 1, tile, tile + 1,
+                     2 * tile + 1})
+    bad |= check_strings(n);
   printf(bad ? "FAILED\n" : "all ok\n");
   return bad;
 }
