@@ -46,6 +46,10 @@ def _lib():
         C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
         C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64,
         C.POINTER(C.c_uint64)]
+    if hasattr(lib, "yb_gpu_scan_group_null_index"):  # as retry_batches below
+        lib.yb_gpu_scan_group_null_index.restype = C.c_int
+        lib.yb_gpu_scan_group_null_index.argtypes = [C.c_void_p,
+                                                     C.POINTER(C.c_int64)]
     lib.yb_gpu_scan_restart_data.restype = C.c_int
     lib.yb_gpu_scan_restart_data.argtypes = [
         C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
@@ -215,12 +219,24 @@ class GpuScan:
                 C.byref(n)), "group_aggregate")
         return keys, vals, cnts, kb, n.value
 
+    def group_null_index(self):
+        """The entry of the last group_aggregate's output that is the
+        NULL-key group, -1 when there is none. Its keys[] value 2**64 - 1 is
+        also the datum of an integer -1 (yb_gpu_scan_group_null_index)."""
+        i = C.c_int64()
+        self._check(
+            self._lib.yb_gpu_scan_group_null_index(self._h, C.byref(i)),
+            "group_null_index")
+        return i.value
+
     def group_aggregate(self, cap=1 << 20, key_bytes_cap=1 << 24):
-        """GROUP BY partial aggregates (spec.group_col must be set)."""
+        """GROUP BY partial aggregates (spec.group_col must be set):
+        {key: (aggs...)}, None keying the NULL group."""
         keys, vals, cnts, kb, n = self.group_aggregate_raw(cap, key_bytes_cap)
         return y._decode_groups(self._spec.schema, self._spec.group_col - 1,
                                 n, keys, vals, cnts, kb,
-                                self._spec.num_aggs, self._spec.aggs)
+                                self._spec.num_aggs, self._spec.aggs,
+                                self.group_null_index())
 
     def restart_data(self):
         """Read-restart data of the last execute/group_aggregate

@@ -107,6 +107,12 @@ void ybg_read_time_init(ybg_read_time_t *rt, uint64_t read_ht,
                         uint64_t local_limit_ht, uint64_t global_limit_ht);
 
 typedef enum {
+  /* Typed compares of the column datum with pred.datum. Integer columns
+   * compare as signed 64-bit (UINT64 values from 2^63 up compare as
+   * negative). FLOAT and DOUBLE columns compare as IEEE 754 has it: -0.0
+   * equals +0.0, and with a NaN on either side every op is false except
+   * NE, which is true; IN and IN_RANGE likewise never match a NaN. A NULL
+   * column fails every predicate. */
   YBG_PRED_GT = 0, YBG_PRED_GE, YBG_PRED_LT, YBG_PRED_LE,
   YBG_PRED_EQ, YBG_PRED_NE,
   /* IN-list membership. NUMERIC column: bytes = n x 8-byte little-endian
@@ -149,9 +155,22 @@ typedef struct {
   uint64_t bytes_len;
 } ybg_pred_t;
 
+/* Unspecified results (they depend on the order in which rows and
+ * partials are folded, which differs between kernels and runs):
+ *  - MIN/MAX_DOUBLE over a column holding NaN: a NaN is kept or dropped
+ *    depending on where it is met (every `<` / `>` with a NaN is false).
+ *  - MIN/MAX_DOUBLE over both +0.0 and -0.0: the result compares equal to
+ *    zero; its sign is unspecified.
+ *  - SUM_DOUBLE whose partial sums round or overflow, e.g. the cancelling
+ *    DBL_MAX, -DBL_MAX, 1.0: any summation order's result may be returned.
+ *    Sums whose every partial sum is exact are bit-reproducible.
+ * COUNT ops and every integer aggregate are exact and order-independent. */
 typedef enum {
   YBG_AGG_COUNT = 0,
   YBG_AGG_COUNT_STAR = 1,
+  /* Sums the column's 64-bit datum (narrow ints sign-extended, UINT32
+   * zero-extended) modulo 2^64: on overflow the result wraps as two's
+   * complement, identically on every execution path. */
   YBG_AGG_SUM_INT64 = 2,
   YBG_AGG_SUM_DOUBLE = 3,
   YBG_AGG_MIN_INT64 = 4,
@@ -270,6 +289,9 @@ int yb_gpu_scan_aggregate(ybg_scan_t *s, ybg_scan_result_t *out);
  * columns (len<<40)|offset into key_bytes. vals/cnts:
  * [n_groups * YBG_MAX_AGGS], aggregate g of group i at i * YBG_MAX_AGGS + g
  * (value bit pattern + non-null contribution count; cnt==0 <=> NULL).
+ * Entries come in no particular order. The group of rows whose group column
+ * is NULL has keys[g] == ~0, which is also the datum of an integer -1:
+ * yb_gpu_scan_group_null_index tells the two apart.
  * Returns 0 and *n_groups on success; error if cap exceeded. Integer
  * aggregates are exact; grouped double SUM uses device atomics and is only
  * reproducible up to summation order. */
@@ -277,6 +299,13 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t *s, uint64_t *keys,
                                 int64_t *vals, uint64_t *cnts,
                                 uint8_t *key_bytes, uint64_t key_bytes_cap,
                                 uint64_t cap, uint64_t *n_groups);
+
+/* Which entry of the yb_gpu_scan_group_aggregate output is the NULL-key
+ * group: *index_out in [0, n_groups), or -1 when no row had a NULL group
+ * column. Every other entry with keys[g] == ~0 is the group of the integer
+ * -1. Valid only when the latest yb_gpu_scan_group_aggregate call on this
+ * handle succeeded; error 4 otherwise. */
+int yb_gpu_scan_group_null_index(ybg_scan_t *s, int64_t *index_out);
 
 /* Materialized row batch (PgTableRow analog — dockv/pg_row.h:91-179).
  * Row order within the batch is by (sort_key) = the row's position in the

@@ -151,14 +151,18 @@ static int grp_cb(const orcl_row_t *row, void *arg) {
 
 /* GROUP BY group_col (value column index). Outputs per group: key datum
  * (numeric; ~0 for the NULL group; strings: (len<<40)|offset into
- * key_bytes_out), vals/cnts [n * ORCL_MAX_AGGS]. Returns 0 ok. */
-int orcl_group_scan(const uint8_t *const *blocks, const size_t *sizes,
-                    size_t nblocks, orcl_kv_format_t fmt,
-                    const orcl_schema_t *schema,
-                    const orcl_scan_spec_t *spec, int group_col,
-                    uint64_t *keys_out, int64_t *vals_out,
-                    uint64_t *cnts_out, uint8_t *key_bytes_out,
-                    size_t key_bytes_cap, size_t cap, size_t *n_out) {
+ * key_bytes_out), vals/cnts [n * ORCL_MAX_AGGS]. The NULL group's ~0 is
+ * also the datum of an integer -1, so *null_index_out (may be NULL) names
+ * the NULL group's entry, -1 without one. Returns 0 ok. */
+int orcl_group_scan_ex(const uint8_t *const *blocks, const size_t *sizes,
+                       size_t nblocks, orcl_kv_format_t fmt,
+                       const orcl_schema_t *schema,
+                       const orcl_scan_spec_t *spec, int group_col,
+                       uint64_t *keys_out, int64_t *vals_out,
+                       uint64_t *cnts_out, uint8_t *key_bytes_out,
+                       size_t key_bytes_cap, size_t cap, size_t *n_out,
+                       int64_t *null_index_out) {
+  if (null_index_out) *null_index_out = -1;
   grp_ctx_t g;
   memset(&g, 0, sizeof(g));
   g.sc = schema;
@@ -183,6 +187,7 @@ int orcl_group_scan(const uint8_t *const *blocks, const size_t *sizes,
       uint64_t kv;
       if (s->key_is_null) {
         kv = ~0ull;
+        if (null_index_out) *null_index_out = (int64_t)n;
       } else if (s->key_bytes) {
         if (boff + s->key_len > key_bytes_cap) {
           rc = -8;
@@ -206,4 +211,17 @@ int orcl_group_scan(const uint8_t *const *blocks, const size_t *sizes,
   free(g.slots);
   *n_out = n;
   return rc;
+}
+
+/* orcl_group_scan_ex without the NULL group's index. */
+int orcl_group_scan(const uint8_t *const *blocks, const size_t *sizes,
+                    size_t nblocks, orcl_kv_format_t fmt,
+                    const orcl_schema_t *schema,
+                    const orcl_scan_spec_t *spec, int group_col,
+                    uint64_t *keys_out, int64_t *vals_out,
+                    uint64_t *cnts_out, uint8_t *key_bytes_out,
+                    size_t key_bytes_cap, size_t cap, size_t *n_out) {
+  return orcl_group_scan_ex(blocks, sizes, nblocks, fmt, schema, spec,
+                            group_col, keys_out, vals_out, cnts_out,
+                            key_bytes_out, key_bytes_cap, cap, n_out, NULL);
 }

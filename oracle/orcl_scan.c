@@ -25,6 +25,8 @@
 #define VT_COL 0x4B          /* 'K' kColumnId */
 #define VT_STRING 0x53       /* 'S' */
 #define VT_FLOAT 0x43        /* 'C' */
+#define VT_UINT32 0x4F       /* 'O' */
+#define VT_UINT64 0x55       /* 'U' */
 #define VT_DOUBLE 0x44       /* 'D' */
 #define VT_FALSE 0x46        /* 'F' */
 #define VT_TRUE 0x54         /* 'T' */
@@ -219,6 +221,20 @@ static int decode_v1_value(const uint8_t *v, size_t len, orcl_dtype_t dt,
       uint64_t u = 0;
       for (int i = 0; i < 8; ++i) u = (u << 8) | v[1 + i];
       *datum = u; /* BE64 of the raw int64 (no sign flip in values) */
+      return 1;
+    }
+    case ORCL_T_UINT32: { /* 4-byte big-endian, zero-extended */
+      if (t != VT_UINT32 || len < 5) return -1;
+      uint32_t u = 0;
+      for (int i = 0; i < 4; ++i) u = (u << 8) | v[1 + i];
+      *datum = u;
+      return 1;
+    }
+    case ORCL_T_UINT64: {
+      if (t != VT_UINT64 || len < 9) return -1;
+      uint64_t u = 0;
+      for (int i = 0; i < 8; ++i) u = (u << 8) | v[1 + i];
+      *datum = u;
       return 1;
     }
     case ORCL_T_FLOAT: {
@@ -535,8 +551,19 @@ static int pred_eval(const orcl_pred_t *pr, const orcl_schema_t *sc,
         if (okl && okh) return 1;
       } else {
         double l, hgh;
-        memcpy(&l, &lo, 8);
-        memcpy(&hgh, &hi, 8);
+        if (!pr->is_key_col &&
+            sc->value_cols[pr->col].dtype == ORCL_T_FLOAT) {
+          /* bounds in the column dtype's bit pattern, like the IN options */
+          uint32_t lu = (uint32_t)lo, hu = (uint32_t)hi;
+          float lf, hf;
+          memcpy(&lf, &lu, 4);
+          memcpy(&hf, &hu, 4);
+          l = lf;
+          hgh = hf;
+        } else {
+          memcpy(&l, &lo, 8);
+          memcpy(&hgh, &hi, 8);
+        }
         int okl = (fl & 1) ? lhs_f >= l : lhs_f > l;
         int okh = (fl & 2) ? lhs_f <= hgh : lhs_f < hgh;
         if (okl && okh) return 1;
@@ -545,7 +572,18 @@ static int pred_eval(const orcl_pred_t *pr, const orcl_schema_t *sc,
     return 0;
   }
   if (numeric == 1) cmp = lhs_i < rhs_i ? -1 : (lhs_i > rhs_i ? 1 : 0);
-  else if (numeric == 2) cmp = lhs_f < rhs_f ? -1 : (lhs_f > rhs_f ? 1 : 0);
+  else if (numeric == 2) {
+    /* IEEE 754: a NaN on either side fails every op but NE */
+    switch (pr->op) {
+      case ORCL_PRED_GT: return lhs_f > rhs_f;
+      case ORCL_PRED_GE: return lhs_f >= rhs_f;
+      case ORCL_PRED_LT: return lhs_f < rhs_f;
+      case ORCL_PRED_LE: return lhs_f <= rhs_f;
+      case ORCL_PRED_EQ: return lhs_f == rhs_f;
+      case ORCL_PRED_NE: return lhs_f != rhs_f;
+      default: return 0;
+    }
+  }
   switch (pr->op) {
     case ORCL_PRED_GT: return cmp > 0;
     case ORCL_PRED_GE: return cmp >= 0;

@@ -49,8 +49,8 @@ def _f64(u):
 
 def fold_groups(case, read_micros, preds, aggs, group_col, group_is_key):
     """Python fold over the rows the oracle scan returns for (preds): the
-    reference for key-column grouping and wherever orcl_group's ~0 NULL
-    marker would collide with a key. Returns ({key: (aggs...)}, rows
+    reference for key-column grouping and, independent of orcl_group, for
+    groups whose key is 2**64 - 1 next to a NULL group. Returns ({key: (aggs...)}, rows
     matched); key = the datum as unsigned 64-bit, None for the NULL group."""
     osc = y.orcl_schema_from(case["schema"])
     ospec = make_orcl_spec(read_micros, preds, ())

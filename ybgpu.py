@@ -304,6 +304,8 @@ class Builder:
             null = True
         elif dt == T_DOUBLE:
             datum = struct.unpack("<Q", struct.pack("<d", value))[0]
+        elif dt == T_FLOAT:
+            datum = struct.unpack("<I", struct.pack("<f", value))[0]
         elif dt == T_STRING:
             buf = C.create_string_buffer(value, len(value))
             self._keepalive.append(buf)
@@ -1056,15 +1058,17 @@ def decode_batch_rows(schema, n_rows, sort_key, key_datums, datums,
 
 
 def _decode_groups(schema, group_col, n, keys, vals, cnts, key_bytes,
-                   num_aggs, aggs):
+                   num_aggs, aggs, null_index=-1):
     """Decode group arrays into {key: (vals...)}; key None for the NULL
-    group; doubles decoded from bit patterns."""
+    group, which is entry null_index (-1: none) — its keys[] value 2**64 - 1
+    is also the datum of an integer -1, which stays a key; doubles decoded
+    from bit patterns."""
     import struct
     out = {}
     is_str = schema.value_cols[group_col].dtype == T_STRING
     for g in range(n):
         kv = keys[g]
-        if kv == (1 << 64) - 1:
+        if g == null_index:
             k = None
         elif is_str:
             off, ln = kv & ((1 << 40) - 1), kv >> 40
@@ -1087,15 +1091,17 @@ def _decode_groups(schema, group_col, n, keys, vals, cnts, key_bytes,
 
 
 def sim_group(spec, data, offsets, n_blocks, cap=1 << 20,
-              key_bytes_cap=1 << 24, return_restart=False):
-    """Host-simulator GROUP BY — TEST INFRASTRUCTURE."""
+              key_bytes_cap=1 << 24, return_restart=False, raw=False):
+    """Host-simulator GROUP BY — TEST INFRASTRUCTURE. raw=True returns
+    (groups, keys, n, null_index): the key array as exported and the entry
+    of the NULL group (-1 without one)."""
     lib = product()
-    f = _sig(lib, "ybg_sim_group", C.c_int,
+    f = _sig(lib, "ybg_sim_group_ex", C.c_int,
              [C.POINTER(ScanSpec), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
               C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
               C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint64,
               C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
-              C.POINTER(C.c_uint32)])
+              C.POINTER(C.c_uint32), C.POINTER(C.c_int64)])
     keys = (C.c_uint64 * cap)()
     vals = (C.c_int64 * (cap * MAX_AGGS))()
     cnts = (C.c_uint64 * (cap * MAX_AGGS))()
@@ -1103,12 +1109,16 @@ def sim_group(spec, data, offsets, n_blocks, cap=1 << 20,
     n = C.c_uint64()
     rht = (C.c_uint8 * MAX_HT)()
     rlen = C.c_uint32()
+    ni = C.c_int64(-1)
     rc = f(C.byref(spec), data, offsets, n_blocks, keys, vals, cnts, kb,
-           key_bytes_cap, cap, C.byref(n), rht, C.byref(rlen))
+           key_bytes_cap, cap, C.byref(n), rht, C.byref(rlen), C.byref(ni))
     if rc != 0:
         raise RuntimeError(f"ybg_sim_group rc={rc}")
     groups = _decode_groups(spec.schema, spec.group_col - 1, n.value, keys,
-                            vals, cnts, kb, spec.num_aggs, spec.aggs)
+                            vals, cnts, kb, spec.num_aggs, spec.aggs,
+                            ni.value)
+    if raw:
+        return groups, keys, n.value, ni.value
     if return_restart:
         return groups, bytes(rht[:rlen.value])
     return groups
@@ -1116,16 +1126,24 @@ def sim_group(spec, data, offsets, n_blocks, cap=1 << 20,
 
 def orcl_group(data, offsets, n_blocks, schema, spec, group_col,
                kv_format=ENC_THREE_SHARED_PARTS, cap=1 << 20,
-               key_bytes_cap=1 << 24, num_aggs=None, aggs=None):
-    """Oracle GROUP BY — TEST INFRASTRUCTURE."""
+               key_bytes_cap=1 << 24, num_aggs=None, aggs=None, raw=False):
+    """Oracle GROUP BY — TEST INFRASTRUCTURE. raw=True as in sim_group.
+    An oracle library built before orcl_group_scan_ex (an older oracle/
+    run with these bindings) does not say which entry is the NULL group.
+    The oracle exports that group last, and it exists exactly when
+    COUNT(*) exceeds COUNT(group column) over the same scan, so a second
+    oracle scan settles it without guessing from the key."""
     lib = oracle()
-    f = _sig(lib, "orcl_group_scan", C.c_int,
-             [C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t),
-              C.c_size_t, C.c_int, C.POINTER(OrclSchema),
-              C.POINTER(OrclScanSpec), C.c_int, C.POINTER(C.c_uint64),
-              C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
-              C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t,
-              C.POINTER(C.c_size_t)])
+    args = [C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t),
+            C.c_size_t, C.c_int, C.POINTER(OrclSchema),
+            C.POINTER(OrclScanSpec), C.c_int, C.POINTER(C.c_uint64),
+            C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
+            C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t,
+            C.POINTER(C.c_size_t)]
+    has_ex = hasattr(lib, "orcl_group_scan_ex")
+    f = _sig(lib, "orcl_group_scan_ex", C.c_int,
+             args + [C.POINTER(C.c_int64)]) if has_ex else \
+        _sig(lib, "orcl_group_scan", C.c_int, args)
     base = C.cast(data, C.c_void_p).value
     blocks = (C.POINTER(C.c_uint8) * n_blocks)()
     sizes = (C.c_size_t * n_blocks)()
@@ -1138,10 +1156,21 @@ def orcl_group(data, offsets, n_blocks, schema, spec, group_col,
     kb = (C.c_uint8 * key_bytes_cap)()
     n = C.c_size_t()
     osc = schema
-    rc = f(blocks, sizes, n_blocks, kv_format, C.byref(osc), C.byref(spec),
-           group_col, keys, vals, cnts, kb, key_bytes_cap, cap, C.byref(n))
+    ni = C.c_int64(-1)
+    call = (blocks, sizes, n_blocks, kv_format, C.byref(osc), C.byref(spec),
+            group_col, keys, vals, cnts, kb, key_bytes_cap, cap, C.byref(n))
+    rc = f(*call, C.byref(ni)) if has_ex else f(*call)
     if rc != 0:
         raise RuntimeError(f"orcl_group_scan rc={rc}")
+    if not has_ex:
+        cspec = OrclScanSpec.from_buffer_copy(spec)
+        cspec.num_aggs = 2
+        cspec.aggs[0] = OrclAgg(AGG_COUNT_STAR, 0)
+        cspec.aggs[1] = OrclAgg(AGG_COUNT, group_col)
+        cres, _ = orcl_scan(data, offsets, n_blocks, schema, cspec,
+                            kv_format=kv_format)
+        star, col = [0 if a.is_null else a.value_i64 for a in cres.aggs[:2]]
+        ni.value = n.value - 1 if star > col else -1
 
     class _S:
         pass
@@ -1149,8 +1178,11 @@ def orcl_group(data, offsets, n_blocks, schema, spec, group_col,
     # adapt orcl schema for the decoder
     sch = _S()
     sch.value_cols = osc.value_cols
-    return _decode_groups(sch, group_col, n.value, keys, vals, cnts, kb,
-                          spec.num_aggs, spec.aggs)
+    groups = _decode_groups(sch, group_col, n.value, keys, vals, cnts, kb,
+                            spec.num_aggs, spec.aggs, ni.value)
+    if raw:
+        return groups, keys, n.value, ni.value
+    return groups
 
 
 def orcl_schema_from(schema):

@@ -1233,6 +1233,21 @@ DEV void row_reset(RowCtxT<NA>* rc, const DevSpec& sp) {
   rc->grp_len = 0;
 }
 
+// GT..NE on two FP values, as IEEE 754 has them: with a NaN on either side
+// every op is false but NE. (A three-way cmp cannot say "unordered": it made
+// a NaN equal to every number.)
+template <typename T>
+DEV bool fp_pred(int op, T a, T b) {
+  switch (op) {
+    case YBG_PRED_GT: return a > b;
+    case YBG_PRED_GE: return a >= b;
+    case YBG_PRED_LT: return a < b;
+    case YBG_PRED_LE: return a <= b;
+    case YBG_PRED_EQ: return a == b;
+    default: return a != b;
+  }
+}
+
 // Value-column predicate compare (pgsql_operation.cc:602-668 typed-compare
 // subset). sptr/slen only for string columns.
 DEV bool pred_compare(const PredC& pr, uint64_t datum, const uint8_t* sptr,
@@ -1340,13 +1355,12 @@ DEV bool pred_compare(const PredC& pr, uint64_t datum, const uint8_t* sptr,
         }
     if (cmp == 0 && slen != rlen) cmp = slen < rlen ? -1 : 1;
   } else if (dtype == YBG_T_DOUBLE) {
-    double a = __longlong_as_double((long long)datum);
-    double b = __longlong_as_double((long long)pr.datum);
-    cmp = a < b ? -1 : (a > b ? 1 : 0);
+    return fp_pred((int)(pr.opdt & 0xff),
+                   __longlong_as_double((long long)datum),
+                   __longlong_as_double((long long)pr.datum));
   } else {
-    float a = __uint_as_float((uint32_t)datum);
-    float b = __uint_as_float((uint32_t)pr.datum);
-    cmp = a < b ? -1 : (a > b ? 1 : 0);
+    return fp_pred((int)(pr.opdt & 0xff), __uint_as_float((uint32_t)datum),
+                   __uint_as_float((uint32_t)pr.datum));
   }
   switch (pr.opdt & 0xff) {
     case YBG_PRED_GT: return cmp > 0;
@@ -2640,13 +2654,12 @@ DEV bool pred_cmp_fast(const PredC& pr, uint64_t datum) {
     int64_t a = (int64_t)datum, b = (int64_t)pr.datum;
     cmp = a < b ? -1 : (a > b ? 1 : 0);
   } else if (dtype == YBG_T_DOUBLE) {
-    double a = __longlong_as_double((long long)datum);
-    double b = __longlong_as_double((long long)pr.datum);
-    cmp = a < b ? -1 : (a > b ? 1 : 0);
+    return fp_pred((int)(pr.opdt & 0xff),
+                   __longlong_as_double((long long)datum),
+                   __longlong_as_double((long long)pr.datum));
   } else {
-    float a = __uint_as_float((uint32_t)datum);
-    float b = __uint_as_float((uint32_t)pr.datum);
-    cmp = a < b ? -1 : (a > b ? 1 : 0);
+    return fp_pred((int)(pr.opdt & 0xff), __uint_as_float((uint32_t)datum),
+                   __uint_as_float((uint32_t)pr.datum));
   }
   switch (pr.opdt & 0xff) {
     case YBG_PRED_GT: return cmp > 0;

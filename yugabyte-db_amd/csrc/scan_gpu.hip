@@ -587,7 +587,8 @@ __global__ void k_group_export(DevSpec sp, GroupCtx gc,
                                uint8_t* __restrict__ out_bytes,
                                uint64_t bytes_cap, uint64_t out_cap,
                                unsigned long long* __restrict__ counters) {
-  // counters[0] = groups, counters[1] = bytes, counters[2] = overflow
+  // counters[0] = groups, counters[1] = bytes, counters[2] = overflow,
+  // counters[3] = 1 + the output slot of the NULL-key group (0: none)
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t n = gc.cap + 1;
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -602,7 +603,10 @@ __global__ void k_group_export(DevSpec sp, GroupCtx gc,
     }
     uint64_t kv = gc.gkey[i];
     if (i == gc.cap) {
-      kv = ~0ull;  // the NULL-key group marker
+      // the NULL-key group: its key reads like the datum of -1, so the
+      // slot is recorded (yb_gpu_scan_group_null_index)
+      kv = ~0ull;
+      counters[3] = slot + 1;
     } else if (grp_is_str) {
       uint32_t len = (uint32_t)(kv >> 40);
       unsigned long long off = atomicAdd(&counters[1], len);
@@ -1156,6 +1160,8 @@ struct ybg_scan {
   unsigned long long* d_gc_out = nullptr;
   uint8_t* d_gb_out = nullptr;
   unsigned long long* d_g_counters = nullptr;
+  int64_t group_null_index = -1;  // of the last successful group_aggregate
+  bool group_done = false;
   // YBG_STAGE=1 transparent mode: columnar snapshot built on the first
   // eligible execute and kept for the handle's lifetime
   ybg_snapshot_t* stage_snap = nullptr;
@@ -2359,13 +2365,14 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t* s, uint64_t* keys,
     HIP_TRY(hipMalloc(&s->gc.poison,
                       (s->group_cap + 1) * YBG_MAX_AGGS * 4));
     HIP_TRY(hipMalloc(&s->gc.overflow, sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&s->d_g_counters, 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&s->d_g_counters, 4 * sizeof(unsigned long long)));
     s->gc.cap = s->group_cap;
     s->gc.data = s->d_data;
     HIP_TRY(hipMalloc(&s->d_gheads, s->n_gheads * sizeof(GroupHead)));
   }
   HIP_TRY(hipMemsetAsync(s->gc.overflow, 0, 8, s->stream));
-  HIP_TRY(hipMemsetAsync(s->d_g_counters, 0, 24, s->stream));
+  s->group_done = false;
+  HIP_TRY(hipMemsetAsync(s->d_g_counters, 0, 32, s->stream));
   HIP_TRY(hipMemsetAsync(s->d_gheads, 0, s->n_gheads * sizeof(GroupHead),
                          s->stream));
   HIP_TRY(hipMemsetAsync(s->d_cont, 0, s->n_gheads * sizeof(uint32_t),
@@ -2421,9 +2428,9 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t* s, uint64_t* keys,
   hipLaunchKernelGGL(k_group_export, dim3(512), dim3(256), 0, s->stream,
                      s->dspec, s->gc, s->d_gk_out, s->d_gv_out, s->d_gc_out,
                      s->d_gb_out, key_bytes_cap, cap, s->d_g_counters);
-  unsigned long long ctr[3];
+  unsigned long long ctr[4];
   unsigned long long errs = 0;
-  HIP_TRY(hipMemcpyAsync(ctr, s->d_g_counters, 24, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(ctr, s->d_g_counters, 32, hipMemcpyDeviceToHost,
                          s->stream));
   HIP_TRY(hipMemcpyAsync(&errs, s->gc.overflow, 8, hipMemcpyDeviceToHost,
                          s->stream));
@@ -2443,6 +2450,15 @@ int yb_gpu_scan_group_aggregate(ybg_scan_t* s, uint64_t* keys,
     HIP_TRY(hipMemcpy(key_bytes, s->d_gb_out,
                       std::min<uint64_t>(ctr[1], key_bytes_cap),
                       hipMemcpyDeviceToHost));
+  s->group_null_index = ctr[3] ? (int64_t)ctr[3] - 1 : -1;
+  s->group_done = true;
+  return 0;
+}
+
+int yb_gpu_scan_group_null_index(ybg_scan_t* s, int64_t* index_out) {
+  if (!s->group_done)
+    return set_err(4, "no successful group_aggregate on this handle");
+  *index_out = s->group_null_index;
   return 0;
 }
 

@@ -539,12 +539,16 @@ int ybg_sim_emit(const ybg_scan_spec_t* spec, const uint8_t* data,
 
 // Sequential GROUP BY simulator: flags pass + grouped pass + export,
 // running the exact device code path.
-int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
-                  const uint64_t* offsets, uint64_t n_blocks,
-                  uint64_t* keys_out, long long* vals_out,
-                  unsigned long long* cnts_out, uint8_t* key_bytes_out,
-                  uint64_t key_bytes_cap, uint64_t cap, uint64_t* n_out,
-                  uint8_t* restart_out, uint32_t* restart_len_out) {
+// null_index_out: the output entry of the NULL-key group, -1 without one
+// (the simulator's yb_gpu_scan_group_null_index).
+int ybg_sim_group_ex(const ybg_scan_spec_t* spec, const uint8_t* data,
+                     const uint64_t* offsets, uint64_t n_blocks,
+                     uint64_t* keys_out, long long* vals_out,
+                     unsigned long long* cnts_out, uint8_t* key_bytes_out,
+                     uint64_t key_bytes_cap, uint64_t cap, uint64_t* n_out,
+                     uint8_t* restart_out, uint32_t* restart_len_out,
+                     int64_t* null_index_out) {
+  if (null_index_out) *null_index_out = -1;
   DevSpec d;
   std::vector<unsigned char> aux;
   build_spec(spec, &d, &aux);
@@ -619,6 +623,7 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
     uint64_t kv = gkey[i];
     if (i == gcap) {
       kv = ~0ull;
+      if (null_index_out) *null_index_out = (int64_t)n;
     } else if (grp_is_str) {
       uint32_t len = (uint32_t)(kv >> 40);
       if (boff + len > key_bytes_cap) return 8;
@@ -643,6 +648,17 @@ int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
   }
   *n_out = n;
   return 0;
+}
+
+int ybg_sim_group(const ybg_scan_spec_t* spec, const uint8_t* data,
+                  const uint64_t* offsets, uint64_t n_blocks,
+                  uint64_t* keys_out, long long* vals_out,
+                  unsigned long long* cnts_out, uint8_t* key_bytes_out,
+                  uint64_t key_bytes_cap, uint64_t cap, uint64_t* n_out,
+                  uint8_t* restart_out, uint32_t* restart_len_out) {
+  return ybg_sim_group_ex(spec, data, offsets, n_blocks, keys_out, vals_out,
+                          cnts_out, key_bytes_out, key_bytes_cap, cap, n_out,
+                          restart_out, restart_len_out, nullptr);
 }
 
 }  // extern "C"
