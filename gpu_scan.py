@@ -102,6 +102,13 @@ def _lib():
             C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64,
             C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64),
             C.POINTER(y.SnapshotSelectResult)]
+    if hasattr(lib, "yb_gpu_snapshot_select_ordered"):  # newer than strings
+        lib.yb_gpu_snapshot_select_ordered.restype = C.c_int
+        lib.yb_gpu_snapshot_select_ordered.argtypes = [
+            C.c_void_p, C.POINTER(y.SnapshotOrder), C.POINTER(C.c_uint64),
+            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64,
+            C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64),
+            C.POINTER(y.SnapshotOrderResult)]
     lib.yb_gpu_snapshot_kernel_ms.restype = C.c_int
     lib.yb_gpu_snapshot_kernel_ms.argtypes = [C.c_void_p,
                                               C.POINTER(C.c_double)]
@@ -470,6 +477,63 @@ class GpuSnapshot:
             preds, cols, limit, backward, row_lo, row_hi, cap)
         return y.decode_snapshot_rows(res, datums, null_masks,
                                       len(cols), cols, cap), res
+
+    def select_ordered_raw(self, preds, cols, order_by, descending=False,
+                           nulls_first=False, limit=0, after=None, row_lo=0,
+                           row_hi=None, cap=1 << 16, varlen_cap=1 << 20,
+                           backward=False):
+        """ORDER BY / top-N on the snapshot
+        (yb_gpu_snapshot_select_ordered): select_var_raw's arrays —
+        (datums, null_masks, row_ids, varlen, varlen_size, result) with a
+        SnapshotOrderResult. order_by: (is_key_col, col); after: a previous
+        result's cursor (y.order_cursor). Errors raise GpuScanError with
+        .code, .result and .varlen_size."""
+        ncols = max(1, min(len(cols), y.MAX_SELECT_COLS))
+        sb = getattr(self, "_order_bufs", None)
+        if sb is None or sb[0] != (cap, ncols, varlen_cap):
+            n = max(cap, 1)
+            sb = ((cap, ncols, varlen_cap), (C.c_uint64 * (n * ncols))(),
+                  (C.c_uint32 * n)(), (C.c_uint64 * n)(),
+                  (C.c_uint8 * max(varlen_cap, 1))())
+            self._order_bufs = sb
+        datums, null_masks, row_ids, varlen = sb[1], sb[2], sb[3], sb[4]
+        q = y.snapshot_order(preds, cols, order_by, descending, nulls_first,
+                             limit, after, row_lo, row_hi, backward)
+        res = y.SnapshotOrderResult()
+        vsize = C.c_uint64()
+        rc = self._lib.yb_gpu_snapshot_select_ordered(
+            self._h, C.byref(q), datums, null_masks, row_ids, cap, varlen,
+            varlen_cap, C.byref(vsize), C.byref(res))
+        if rc:
+            err = GpuScanError(
+                f"snapshot_select_ordered rc={rc}: "
+                f"{self._lib.yb_gpu_last_error().decode()}")
+            err.code = rc
+            err.result = res
+            err.varlen_size = vsize.value
+            raise err
+        return datums, null_masks, row_ids, varlen, vsize.value, res
+
+    def select_ordered(self, preds, cols, order_by, descending=False,
+                       nulls_first=False, limit=0, after=None, row_lo=0,
+                       row_hi=None, cap=1 << 16, varlen_cap=1 << 20):
+        """SELECT cols WHERE preds ORDER BY order_by [DESC] LIMIT limit on
+        the snapshot: returns (rows, cursor, result). rows as select()'s;
+        cursor is the last delivered row's place in the order (None when
+        nothing was delivered): pass it as `after` for the next page until
+        result.r.done. Ties are broken by snapshot position, ascending."""
+        strs = None
+        if self._schema is not None and len(cols) <= y.MAX_SELECT_COLS:
+            try:
+                strs = y.select_string_cols(self._schema, cols)
+            except IndexError:  # out of range: the ABI names the offender
+                strs = None
+        datums, null_masks, _ids, varlen, _vs, res = self.select_ordered_raw(
+            preds, cols, order_by, descending, nulls_first, limit, after,
+            row_lo, row_hi, cap, varlen_cap)
+        rows = y.decode_snapshot_rows(res.r, datums, null_masks, len(cols),
+                                      cols, cap, varlen, strs)
+        return rows, y.order_cursor(res), res
 
     def kernel_ms(self):
         ms = C.c_double()

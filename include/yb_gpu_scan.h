@@ -677,6 +677,97 @@ int yb_gpu_snapshot_select_var(ybg_snapshot_t *sn, const ybg_snapshot_select_t *
  * it). */
 uint64_t ybg_snapshot_select_tile_rows(void);
 
+/* ORDER BY / top-N on a snapshot: the matching rows of a window ordered by
+ * one numeric value or key column, the first row_limit of them delivered,
+ * with a cursor for the next page.
+ *
+ *   yb_gpu_snapshot_select_ordered ~ the sort node ABOVE
+ *                            PgsqlReadOperation::ExecuteScalar
+ *                            (pgsql_operation.cc:2808-2931), which the
+ *                            reference does NOT push down to the tablet: like
+ *                            GROUP BY this is the snapshot contract's own
+ *                            extension, not a transcription.
+ */
+typedef struct {
+  ybg_snapshot_select_t sel;     /* preds, projection, window [row_lo,row_hi), row_limit (0 = all);
+                                    sel.backward must be 0 (error 9) */
+  int32_t order_is_key_col, order_col;   /* as ybg_pred_t.is_key_col / .col */
+  int32_t descending;            /* 0 ASC, 1 DESC */
+  int32_t nulls_first;           /* 0: NULLs after every value (both directions), 1: before */
+  int32_t have_cursor;           /* 1: deliver only rows strictly after the cursor in the order */
+  int32_t cursor_is_null;
+  uint64_t cursor_datum, cursor_row;
+} ybg_snapshot_order_t;
+
+typedef struct {
+  ybg_snapshot_select_result_t r;  /* n_rows delivered; rows_scanned = window positions;
+                                      rows_matched = matching rows of the window that lie after the
+                                      cursor; done = (n_rows == rows_matched); resume_row unused (0) */
+  int32_t  cursor_is_null; uint64_t cursor_datum, cursor_row;  /* last delivered row; valid if n_rows > 0 */
+  uint32_t digit_passes;           /* selection passes that ran (0: no selection was needed) */
+} ybg_snapshot_order_result_t;
+
+/* Synchronous, on the snapshot's own stream. Output arrays, projection
+ * rules, string projection and the error-8 handling are
+ * yb_gpu_snapshot_select_var's: datums column-major with stride cap, a
+ * NULL's datum 0, null_masks masked to the projection, a projected string
+ * column (string-staged snapshot) on the canonical varlen heap in delivery
+ * order. With no string column projected varlen may be NULL with
+ * varlen_cap 0. row_ids[i] is delivered row i's snapshot position.
+ * The order is total (no two rows tie): three components, compared
+ *   lexicographically.
+ *   1. NULL class: a row whose order column is NULL sorts after every
+ *      non-NULL row, or before with nulls_first; descending does not move
+ *      it. Key columns are never NULL.
+ *   2. value: integer, bool and key columns compare as signed 64-bit datums
+ *      (the predicates' rule; UINT64 values from 2^63 up sort as negative).
+ *      DOUBLE and FLOAT (float bits in the datum's low 32 bits) compare
+ *      numerically with -0.0 == +0.0 and every NaN equal to every other NaN
+ *      and greater than every number, +inf included (PostgreSQL's rule), so
+ *      under DESC the NaNs come first among the non-NULLs. descending
+ *      reverses this component only.
+ *   3. snapshot position, ascending in BOTH directions (ORDER BY col DESC,
+ *      <tablet key> ASC): the result is the stable sort of the key-order
+ *      select.
+ *   Delivered datums are the rows' own bit patterns (a NaN keeps its
+ *   payload, -0.0 stays -0.0).
+ * Limit and paging: the first row_limit rows of the order are delivered
+ *   (0 = all). out->cursor_* is the last delivered row's NULL class, order
+ *   datum and position; passed back with have_cursor = 1 only rows strictly
+ *   after it are eligible, and the concatenated pages equal the unlimited
+ *   result exactly. cursor_datum goes through the same value mapping (a -0.0
+ *   cursor stands for the zero class, any NaN for the NaN class).
+ * digit_passes: histogram passes of the radix select that ran (8-bit
+ *   digits, at most 12). 0 when no selection was needed: row_limit 0, or a
+ *   limit at or above the eligible count. The eligible count comes from the
+ *   count pass, or with a cursor from one marking pass over the matches.
+ * Errors: 9, naming the offender, launching nothing and leaving the snapshot
+ *   usable, for everything yb_gpu_snapshot_select_var rejects,
+ *   sel.backward != 0, a STRING or out-of-range order column and
+ *   cursor_row >= 2^32. 8 when cap (r.n_rows then holds the count needed) or
+ *   varlen_cap (*varlen_size the size needed) is too small. 10 device.
+ * An empty snapshot, an empty window or no eligible row returns zero rows,
+ *   done = 1 and digit_passes = 0.
+ * Determinism: datums, null_masks, row_ids and the heap are byte-identical
+ *   across repeated calls, across separately built snapshots of one tablet
+ *   and across every setting of YBG_SNAP_ORDER_CAND.
+ * Memory: the selection scratch (a second bitmap and tile arrays, the digit
+ *   histogram) is allocated by the first ordered select, the candidate and
+ *   sort buffers are grown on demand; ybg_snapshot_info_t.device_bytes
+ *   includes them from then on. The select's bitmap, tile arrays and output
+ *   buffers are shared.
+ * yb_gpu_snapshot_kernel_ms then reports every launch of the call. */
+int yb_gpu_snapshot_select_ordered(ybg_snapshot_t *sn, const ybg_snapshot_order_t *q,
+                                   uint64_t *datums, uint32_t *null_masks, uint64_t *row_ids,
+                                   uint64_t cap, uint8_t *varlen, uint64_t varlen_cap,
+                                   uint64_t *varlen_size, ybg_snapshot_order_result_t *out);
+/* Default early-out threshold of the ordered select: the radix select stops
+ * descending once the bucket that holds the limit-th row has at most this
+ * many rows; the rows at or below the bucket are then compacted and sorted.
+ * YBG_SNAP_ORDER_CAND=n in the environment (read per call) overrides it;
+ * n = 1 switches the early-out off (every digit pass runs). */
+uint64_t ybg_snapshot_order_candidate_rows(void);
+
 /* Device time (events) of the last query: query kernel + final reduce. */
 int yb_gpu_snapshot_kernel_ms(ybg_snapshot_t *sn, double *query_ms);
 int yb_gpu_snapshot_close(ybg_snapshot_t *sn);

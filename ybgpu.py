@@ -877,6 +877,98 @@ def sim_snapshot_select_var(spec, data, offsets, n_blocks, preds, cols,
     return (datums, null_masks, row_ids, varlen, vsize.value), res
 
 
+class SnapshotOrder(C.Structure):
+    """ybg_snapshot_order_t."""
+    _fields_ = [("sel", SnapshotSelect),
+                ("order_is_key_col", C.c_int32), ("order_col", C.c_int32),
+                ("descending", C.c_int32), ("nulls_first", C.c_int32),
+                ("have_cursor", C.c_int32), ("cursor_is_null", C.c_int32),
+                ("cursor_datum", C.c_uint64), ("cursor_row", C.c_uint64)]
+
+
+class SnapshotOrderResult(C.Structure):
+    """ybg_snapshot_order_result_t."""
+    _fields_ = [("r", SnapshotSelectResult),
+                ("cursor_is_null", C.c_int32),
+                ("cursor_datum", C.c_uint64), ("cursor_row", C.c_uint64),
+                ("digit_passes", C.c_uint32)]
+
+
+def snapshot_order(preds, cols, order_by, descending=False,
+                   nulls_first=False, limit=0, after=None, row_lo=0,
+                   row_hi=None, backward=False):
+    """Pack an ordered snapshot select. order_by: (is_key_col, col);
+    after: the cursor (is_null, datum, row) a previous result carried
+    (order_cursor), or None."""
+    q = SnapshotOrder()
+    q.sel = snapshot_select(preds, cols, limit, backward, row_lo, row_hi)
+    q.order_is_key_col = 1 if order_by[0] else 0
+    q.order_col = order_by[1]
+    q.descending = 1 if descending else 0
+    q.nulls_first = 1 if nulls_first else 0
+    if after is not None:
+        q.have_cursor = 1
+        q.cursor_is_null = 1 if after[0] else 0
+        q.cursor_datum = after[1]
+        q.cursor_row = after[2]
+    return q
+
+
+def order_cursor(res):
+    """The cursor of an ordered select's result (the last delivered row), to
+    pass as `after`; None when nothing was delivered."""
+    if not res.r.n_rows:
+        return None
+    return (res.cursor_is_null, res.cursor_datum, res.cursor_row)
+
+
+def snapshot_order_candidate_rows():
+    """Default early-out threshold of the ordered select
+    (ybg_snapshot_order_candidate_rows)."""
+    return _sig(product(), "ybg_snapshot_order_candidate_rows", C.c_uint64,
+                [])()
+
+
+def sim_snapshot_select_ordered(spec, data, offsets, n_blocks, preds, cols,
+                                order_by, descending=False,
+                                nulls_first=False, limit=0, after=None,
+                                row_lo=0, row_hi=None, cap=1 << 16,
+                                varlen_cap=1 << 20, strings=False,
+                                backward=False):
+    """Host SIMULATOR of yb_gpu_snapshot_select_ordered
+    (ybg_sim_snapshot_select_ordered) — TEST INFRASTRUCTURE, as
+    sim_snapshot_select_var. Returns ((datums, null_masks, row_ids, varlen,
+    varlen_size) raw arrays, SnapshotOrderResult); raises RuntimeError
+    carrying .code, .result and .varlen_size on a non-zero code."""
+    lib = product()
+    f = _sig(lib, "ybg_sim_snapshot_select_ordered", C.c_int,
+             [C.POINTER(ScanSpec), C.POINTER(C.c_uint8),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(SnapshotOrder),
+              C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+              C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8),
+              C.c_uint64, C.POINTER(C.c_uint64),
+              C.POINTER(SnapshotOrderResult)])
+    q = snapshot_order(preds, cols, order_by, descending, nulls_first, limit,
+                       after, row_lo, row_hi, backward)
+    n = max(cap, 1)
+    datums = (C.c_uint64 * (n * max(1, min(len(cols), MAX_SELECT_COLS))))()
+    null_masks = (C.c_uint32 * n)()
+    row_ids = (C.c_uint64 * n)()
+    varlen = (C.c_uint8 * max(varlen_cap, 1))()
+    vsize = C.c_uint64()
+    res = SnapshotOrderResult()
+    rc = f(C.byref(spec), data, offsets, n_blocks, C.byref(q),
+           1 if strings else 0, datums, null_masks, row_ids, cap, varlen,
+           varlen_cap, C.byref(vsize), C.byref(res))
+    if rc != 0:
+        err = RuntimeError(f"ybg_sim_snapshot_select_ordered failed rc={rc}")
+        err.code = rc
+        err.result = res
+        err.varlen_size = vsize.value
+        raise err
+    return (datums, null_masks, row_ids, varlen, vsize.value), res
+
+
 def sim_scan_fast(spec, data, offsets, n_blocks):
     """Host simulator of the SPECIALIZED fast batch scanner
     (scan_batch_fast + general fallback per aborted batch) — TEST

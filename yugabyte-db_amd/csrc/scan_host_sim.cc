@@ -1209,3 +1209,243 @@ int ybg_sim_snapshot_select_var(
 }
 
 }  // extern "C"
+
+namespace {
+
+// The simulated lane (tile, lane): its two match bits and row pair, as
+// snap_order_load hands them to the kernels.
+struct SimOrderLane {
+  uint32_t two;
+  uint64_t r0, v[kSnapVec];
+  uint32_t nm[kSnapVec];
+};
+
+SimOrderLane sim_order_load(const SnapOrder& o, const uint64_t* bitmap,
+                            uint64_t tile, uint32_t lane) {
+  SimOrderLane l;
+  const uint32_t b = lane * kSnapVec;
+  const uint64_t w = bitmap[tile * kSnapTileWords + (b >> 6)];
+  l.two = (uint32_t)(w >> (b & 63)) & 3u;
+  l.r0 = tile * kSnapTileRows + b;
+  for (int k = 0; k < kSnapVec; ++k) {
+    l.v[k] = l.two ? o.col[l.r0 + k] : 0;
+    l.nm[k] = (l.two && o.nullmask) ? o.nullmask[l.r0 + k] : 0u;
+  }
+  return l;
+}
+
+// k_snap_order_hist, the tiles walked serially.
+void sim_order_hist(const SnapOrder& o, const SnapWindow& win, int pass,
+                    const SnapOrderState& st, const uint64_t* bitmap,
+                    const uint64_t* tile_cnt, uint64_t* bins) {
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    if (tile_cnt[t] == 0) continue;
+    for (uint32_t lane = 0; lane < (uint32_t)kSnapThreads; ++lane) {
+      const SimOrderLane l = sim_order_load(o, bitmap, win.tile_lo + t, lane);
+      for (int k = 0; k < kSnapVec; ++k) {
+        SnapOrderKey key;
+        if (snap_order_row(o, l.v[k], l.nm[k], l.r0 + k, (l.two >> k) & 1u,
+                           &key) &&
+            snap_order_in_bucket(key, st))
+          ++bins[snap_order_digit(key, pass)];
+      }
+    }
+  }
+}
+
+// k_snap_order_fix, serially; the bins are left zeroed.
+void sim_order_fix(int pass, uint64_t limit, uint64_t* bins,
+                   SnapOrderState* st) {
+  uint64_t total = 0;
+  for (int i = 0; i < kSnapOrderBins; ++i) total += bins[i];
+  const bool go = pass != 0 || snap_order_begin(st, total, limit);
+  uint64_t excl = 0;
+  for (int i = 0; i < kSnapOrderBins && go; ++i) {
+    const uint64_t cnt = bins[i];
+    if (cnt && excl < st->k && st->k <= excl + cnt) {
+      snap_order_advance(st, pass, (uint32_t)i, excl, cnt);
+      break;
+    }
+    excl += cnt;
+  }
+  for (int i = 0; i < kSnapOrderBins; ++i) bins[i] = 0;
+}
+
+// k_snap_order_mark + k_snap_select_scan; returns the selected total.
+uint64_t sim_order_mark(const SnapOrder& o, const SnapWindow& win,
+                        const SnapOrderState& st, const uint64_t* bitmap,
+                        const uint64_t* tile_cnt, uint64_t* sel_bitmap,
+                        uint64_t* sel_cnt, uint32_t* tile_off) {
+  uint64_t total = 0;
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    const uint64_t tile = win.tile_lo + t;
+    uint64_t cnt = 0;
+    for (int wave = 0; wave < kSnapThreads / 64 && tile_cnt[t]; ++wave) {
+      uint64_t b[kSnapVec] = {0, 0};
+      for (uint32_t lane = 0; lane < 64; ++lane) {
+        const SimOrderLane l =
+            sim_order_load(o, bitmap, tile, (uint32_t)wave * 64 + lane);
+        for (int k = 0; k < kSnapVec; ++k) {
+          SnapOrderKey key;
+          if (snap_order_row(o, l.v[k], l.nm[k], l.r0 + k, (l.two >> k) & 1u,
+                             &key) &&
+              snap_order_selected(key, st))
+            b[k] |= 1ull << lane;
+        }
+      }
+      snap_select_pack(b[0], b[1],
+                       sel_bitmap + tile * kSnapTileWords + wave * 2);
+      cnt |= (uint64_t)(snap_popc64(b[0]) + snap_popc64(b[1])) << (16 * wave);
+    }
+    sel_cnt[t] = cnt;
+    tile_off[t] = (uint32_t)total;
+    total += snap_select_tile_count(cnt);
+  }
+  return total;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Ordered-select simulator: yb_gpu_snapshot_select_ordered's contract (codes
+// 8 / 9 included) from the same key, digit, state, gather and emit code; the
+// tiles are walked serially and std::stable_sort stands in for the device
+// radix sort. Honours YBG_SNAP_ORDER_CAND.
+int ybg_sim_snapshot_select_ordered(
+    const ybg_scan_spec_t* spec, const uint8_t* data, const uint64_t* offsets,
+    uint64_t n_blocks, const ybg_snapshot_order_t* query, int stage_strings,
+    uint64_t* datums, uint32_t* null_masks, uint64_t* row_ids, uint64_t cap,
+    uint8_t* varlen, uint64_t varlen_cap, uint64_t* varlen_size,
+    ybg_snapshot_order_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  uint64_t vs_local = 0;
+  if (!varlen_size) varlen_size = &vs_local;
+  *varlen_size = 0;
+  SimSnapshot snap;
+  int rc = sim_snapshot_build(spec, data, offsets, n_blocks, &snap,
+                              stage_strings != 0);
+  if (rc) return rc;
+  const uint64_t n_rows = snap.n;
+  SnapQuery q;
+  SnapSelect sel;
+  SnapOrder ord;
+  std::vector<uint8_t> aux;
+  char err[192];
+  rc = snap_build_order(spec->schema, &snap.cols, *query, n_rows, &aux, &q,
+                        &sel, &ord, err, sizeof(err));
+  if (rc) return rc;
+  q.aux = aux.data();
+  out->r.entries_seen = snap.stats.entries_seen;
+  memcpy(out->r.restart_ht, snap.stats.restart_ht,
+         snap.stats.restart_ht_len);
+  out->r.restart_ht_len = snap.stats.restart_ht_len;
+  const uint64_t hi = query->sel.row_hi < n_rows ? query->sel.row_hi : n_rows;
+  const uint64_t lo = query->sel.row_lo;
+  if (lo >= hi) {
+    snap_order_fill(lo, hi, 0, 0, 0, nullptr, out);
+    return 0;
+  }
+  const uint64_t limit = query->sel.row_limit;
+  const uint64_t cand = snap_order_cand_env();
+  const SnapWindow win = snap_select_window(lo, hi);
+  const uint64_t tiles = (n_rows + kSnapTileRows - 1) / kSnapTileRows;
+  std::vector<uint64_t> bitmap(tiles * kSnapTileWords, 0);
+  std::vector<uint64_t> sel_bitmap(tiles * kSnapTileWords, 0);
+  std::vector<uint64_t> tile_cnt(win.n_tiles), sel_cnt(win.n_tiles);
+  std::vector<uint32_t> tile_off(win.n_tiles);
+  const int v = (q.any_nullable ? 2 : 0) | (q.general ? 1 : 0);
+  switch (v) {
+    case 0: sim_select_count<false, kSnapGenFast>(q, win, bitmap.data(),
+                                                  tile_cnt.data()); break;
+    case 1: sim_select_count<false, kSnapGenStr>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
+    case 2: sim_select_count<true, kSnapGenFast>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
+    default: sim_select_count<true, kSnapGenStr>(q, win, bitmap.data(),
+                                                 tile_cnt.data()); break;
+  }
+  SnapOrderState st;
+  memset(&st, 0, sizeof(st));
+  uint64_t bins[kSnapOrderBins] = {0};
+  // eligible rows: the matches, or with a cursor the matches after it
+  bool marked = ord.have_cursor != 0;
+  uint64_t eligible = 0;
+  if (marked) {
+    eligible = sim_order_mark(ord, win, st, bitmap.data(), tile_cnt.data(),
+                              sel_bitmap.data(), sel_cnt.data(),
+                              tile_off.data());
+  } else {
+    for (uint64_t t = 0; t < win.n_tiles; ++t) {
+      tile_off[t] = (uint32_t)eligible;
+      eligible += snap_select_tile_count(tile_cnt[t]);
+    }
+  }
+  const uint64_t n = (limit && limit < eligible) ? limit : eligible;
+  if (n > cap) {
+    snap_order_fill(lo, hi, n, eligible, 0, nullptr, out);
+    out->r.done = 0;
+    return 8;
+  }
+  if (n == 0) {
+    snap_order_fill(lo, hi, 0, 0, 0, nullptr, out);
+    return 0;
+  }
+  uint32_t passes = 0;
+  uint64_t c = eligible;
+  if (n < eligible) {
+    for (int pass = 0; pass < kSnapOrderPasses; ++pass) {
+      sim_order_hist(ord, win, pass, st, bitmap.data(), tile_cnt.data(), bins);
+      sim_order_fix(pass, limit, bins, &st);
+      ++passes;
+      if (!snap_order_more(st, limit, cand)) break;
+    }
+    c = sim_order_mark(ord, win, st, bitmap.data(), tile_cnt.data(),
+                       sel_bitmap.data(), sel_cnt.data(), tile_off.data());
+    marked = true;
+  }
+  if (c < n) return 10;
+  // k_snap_order_gather, the sort(s), k_snap_order_emit
+  std::vector<uint64_t> ckey(c), cval(c);
+  const uint64_t* gb = marked ? sel_bitmap.data() : bitmap.data();
+  const uint64_t* gc = marked ? sel_cnt.data() : tile_cnt.data();
+  for (uint64_t t = 0; t < win.n_tiles; ++t) {
+    if (snap_select_tile_count(gc[t]) == 0) continue;
+    const uint64_t tile = win.tile_lo + t;
+    for (uint32_t lane = 0; lane < (uint32_t)kSnapThreads; ++lane)
+      snap_order_gather_pair(ord, gb + tile * kSnapTileWords, tile,
+                             tile_off[t], lane * kSnapVec, ckey.data(),
+                             cval.data());
+  }
+  std::vector<uint64_t> idx(c);
+  for (uint64_t i = 0; i < c; ++i) idx[i] = i;
+  std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+    return ckey[a] < ckey[b];
+  });
+  if (ord.nullmask)
+    std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+      return (cval[a] >> 32) < (cval[b] >> 32);
+    });
+  const SnapSelectOut so = {row_ids, null_masks, datums, cap};
+  SnapOrderCursor cur;
+  memset(&cur, 0, sizeof(cur));
+  for (uint64_t i = 0; i < n; ++i)
+    snap_order_emit(ord, sel, so, cval[idx[i]], i, n, &cur);
+  if (sel.num_str) {
+    std::vector<uint64_t> row_off(n + 1, 0);
+    for (uint64_t i = 0; i < n; ++i)
+      row_off[i + 1] = row_off[i] + snap_select_row_strlen(sel, so, i);
+    *varlen_size = row_off[n];
+    if (row_off[n] > varlen_cap) {
+      snap_order_fill(lo, hi, n, eligible, passes, nullptr, out);
+      out->r.done = 0;
+      return 8;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+      snap_select_strcopy_row(sel, so, i, row_off[i], varlen);
+  }
+  snap_order_fill(lo, hi, n, eligible, passes, &cur, out);
+  return 0;
+}
+
+}  // extern "C"

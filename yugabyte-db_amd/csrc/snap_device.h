@@ -1,8 +1,9 @@
 // yugabyte-db_amd/csrc/snap_device.h — columnar-snapshot query logic: the
 // per-row predicate/aggregate evaluation over dense per-column arrays, the
 // grouped query's accumulate / flush / export, the select's per-tile bit
-// packing / rank / output index / emit, and the host-side translation of an
-// ABI query into the POD kernel argument.
+// packing / rank / output index / emit, the ordered select's key image /
+// digit / selection state / gather / emit, and the host-side translation of
+// an ABI query into the POD kernel argument.
 // Compiled into the HIP query kernels (snap_gpu.hip) AND the host simulator
 // (scan_host_sim.cc), with the same DEV macro convention as scan_device.h.
 //
@@ -764,6 +765,243 @@ DEV void snap_select_gather_pair(const SnapSelect& s, const SnapSelectOut& o,
 }
 
 // ---------------------------------------------------------------------------
+// ORDER BY / top-N on a snapshot: a radix select between the select's match
+// bitmap and its emit. Every row has a selection key that cannot tie,
+//   (NULL class: 1 bit, value image: 64 bits, position: 32 bits),
+// compared lexicographically, so "the first n rows of the order" is "the
+// rows whose key is <= the n-th smallest key" and no tie ranking exists.
+//   hist:  one digit of the key per pass, most significant first: pass 0 is
+//     the NULL class plus the image's top byte (9 bits), passes 1..7 the
+//     other image bytes, passes 8..11 the position bytes. A pass counts the
+//     matched, eligible (after the cursor) rows whose higher digits equal
+//     the prefix fixed so far.
+//   fix:   one workgroup prefix-sums the bins, fixes the digit that holds
+//     the k-th key and writes the SnapOrderState for the next pass and the
+//     host.
+//   mark:  rows whose key prefix is <= the fixed prefix ("selected") become
+//     a second bitmap with the select's per-tile counts; the select's scan
+//     turns those into offsets.
+//   gather / sort / emit: the selected rows' (image, class | position) pairs
+//     in position order, a stable radix sort on the image (and one more bit
+//     for the class), snap_select_emit of the first n.
+// 8-bit digits: a 256-bin (512 for pass 0) workgroup histogram is 2 KiB of
+// LDS, so four workgroups per CU stay resident like every other snapshot
+// kernel, the flush is at most 512 global adds per workgroup, and the fix
+// kernel is one 512-thread scan. 11-bit digits would save three of the
+// twelve passes at full depth, but full depth is the rare case (the
+// early-out below usually stops after one or two passes) and the 2048-bin
+// flush per workgroup would cost every pass.
+// ---------------------------------------------------------------------------
+constexpr int kSnapOrderBins = 512;
+constexpr int kSnapOrderPasses = 12;
+// default early-out threshold (ybg_snapshot_order_candidate_rows)
+constexpr uint64_t kSnapOrderCand = 1ull << 20;
+constexpr int kSnapOrderInt = 0, kSnapOrderDouble = 1, kSnapOrderFloat = 2;
+
+struct SnapOrderKey {
+  uint64_t img;
+  uint32_t pos;
+  uint32_t cls;
+};
+
+// The order kernels' argument (POD, passed by value).
+struct SnapOrder {
+  const uint64_t* col;       // staged order column
+  const uint32_t* nullmask;  // nullptr: the order column holds no NULL
+  uint32_t null_m;
+  int32_t kind;              // kSnapOrderInt / Double / Float
+  int32_t descending, nulls_first, have_cursor;
+  uint32_t pad_;
+  SnapOrderKey cursor;
+};
+
+// Selection state, device resident; written by the fix step only.
+struct SnapOrderState {
+  SnapOrderKey prefix;  // digits fixed so far, the rest zero
+  uint64_t img_mask;    // bits of the key the fixed digits cover
+  uint32_t pos_mask;
+  uint32_t cls_mask;
+  uint64_t k;         // the wanted key is the k-th (1-based) of the bucket
+  uint64_t below;     // eligible rows whose prefix is below the fixed one
+  uint64_t bucket;    // eligible rows whose prefix equals it
+  uint64_t eligible;  // matched rows after the cursor (pass 0's total)
+  uint32_t depth;     // digits fixed
+  uint32_t pad_;
+};
+
+// 64-bit image of an order datum: unsigned order of the images = the value
+// order of the contract. Integers flip the sign bit; doubles and floats are
+// canonicalised (-0.0 -> +0.0, every NaN -> the quiet NaN above +inf) and
+// sign-magnitude -> biased; a float's 32 ordered bits sit in the image's
+// high half so the first passes already split them. DESC complements.
+YBG_HD uint64_t snap_order_image(int kind, uint64_t datum, int descending) {
+  uint64_t img;
+  if (kind == kSnapOrderDouble) {
+    uint64_t d = datum;
+    if ((d & 0x7fffffffffffffffull) > 0x7ff0000000000000ull)
+      d = 0x7ff8000000000000ull;
+    else if (d == 0x8000000000000000ull)
+      d = 0;
+    img = d ^ ((d >> 63) ? ~0ull : (1ull << 63));
+  } else if (kind == kSnapOrderFloat) {
+    uint32_t f = (uint32_t)datum;
+    if ((f & 0x7fffffffu) > 0x7f800000u)
+      f = 0x7fc00000u;
+    else if (f == 0x80000000u)
+      f = 0;
+    img = (uint64_t)(f ^ ((f >> 31) ? 0xffffffffu : 0x80000000u)) << 32;
+  } else {
+    img = datum ^ (1ull << 63);
+  }
+  return descending ? ~img : img;
+}
+
+// Key of a row (or of the cursor). A NULL's image is 0: NULL rows differ by
+// position only.
+YBG_HD SnapOrderKey snap_order_key(const SnapOrder& o, uint64_t datum,
+                                   bool is_null, uint64_t pos) {
+  SnapOrderKey k;
+  k.cls = (is_null ? 1u : 0u) ^ (o.nulls_first ? 1u : 0u);
+  k.img = is_null ? 0 : snap_order_image(o.kind, datum, o.descending);
+  k.pos = (uint32_t)pos;
+  return k;
+}
+
+YBG_HD bool snap_order_is_null(const SnapOrder& o, uint32_t cls) {
+  return (cls ^ (o.nulls_first ? 1u : 0u)) != 0;
+}
+
+// a > b
+YBG_HD bool snap_order_after(const SnapOrderKey& a, const SnapOrderKey& b) {
+  if (a.cls != b.cls) return a.cls > b.cls;
+  if (a.img != b.img) return a.img > b.img;
+  return a.pos > b.pos;
+}
+
+// Key of one row and whether it takes part: matched (its bit of the match
+// bitmap) and, with a cursor, strictly after it.
+YBG_HD bool snap_order_row(const SnapOrder& o, uint64_t datum, uint32_t nm,
+                           uint64_t pos, bool matched, SnapOrderKey* k) {
+  *k = snap_order_key(o, datum, (nm & o.null_m) != 0, pos);
+  return matched && (!o.have_cursor || snap_order_after(*k, o.cursor));
+}
+
+YBG_HD uint32_t snap_order_digit(const SnapOrderKey& k, int pass) {
+  if (pass == 0) return (k.cls << 8) | (uint32_t)(k.img >> 56);
+  if (pass < 8) return (uint32_t)(k.img >> (56 - 8 * pass)) & 0xffu;
+  return (k.pos >> (24 - 8 * (pass - 8))) & 0xffu;
+}
+
+// The key's fixed digits equal the prefix.
+YBG_HD bool snap_order_in_bucket(const SnapOrderKey& k,
+                                 const SnapOrderState& st) {
+  return (((k.img ^ st.prefix.img) & st.img_mask) |
+          ((k.pos ^ st.prefix.pos) & st.pos_mask) |
+          ((k.cls ^ st.prefix.cls) & st.cls_mask)) == 0;
+}
+
+// The key's fixed digits are at or below the prefix: the row is delivered or
+// still a candidate. With every digit fixed this is "key <= the k-th key".
+YBG_HD bool snap_order_selected(const SnapOrderKey& k,
+                                const SnapOrderState& st) {
+  const uint32_t c = k.cls & st.cls_mask;
+  if (c != st.prefix.cls) return c < st.prefix.cls;
+  const uint64_t i = k.img & st.img_mask;
+  if (i != st.prefix.img) return i < st.prefix.img;
+  return (k.pos & st.pos_mask) <= st.prefix.pos;
+}
+
+// Fix step of pass `pass`, given the winning digit: `excl` bucket rows lie
+// in lower bins, `cnt` in the digit's own (excl < st->k <= excl + cnt).
+YBG_HD void snap_order_advance(SnapOrderState* st, int pass, uint32_t digit,
+                               uint64_t excl, uint64_t cnt) {
+  st->below += excl;
+  st->k -= excl;
+  st->bucket = cnt;
+  if (pass == 0) {
+    st->prefix.cls = digit >> 8;
+    st->prefix.img = (uint64_t)(digit & 0xffu) << 56;
+  } else if (pass < 8) {
+    st->prefix.img |= (uint64_t)digit << (56 - 8 * pass);
+  } else {
+    st->prefix.pos |= digit << (24 - 8 * (pass - 8));
+  }
+  const int depth = pass + 1;
+  st->depth = (uint32_t)depth;
+  st->cls_mask = 1u;
+  st->img_mask = depth >= 8 ? ~0ull : ~0ull << (64 - 8 * depth);
+  st->pos_mask = depth <= 8 ? 0u : ~0u << (32 - 8 * (depth - 8));
+}
+
+// Pass 0 learns the eligible count: `total` rows, of which the first
+// min(limit, total) are wanted. False: every eligible row is delivered and
+// the state stays at depth 0 (everything "selected").
+YBG_HD bool snap_order_begin(SnapOrderState* st, uint64_t total,
+                             uint64_t limit) {
+  st->eligible = total;
+  st->bucket = total;
+  st->k = (limit && limit < total) ? limit : total;
+  return limit && limit < total;
+}
+
+// Host: are more digit passes needed after the state the fix step wrote?
+// cand: the early-out threshold (< 2: off).
+YBG_HD bool snap_order_more(const SnapOrderState& st, uint64_t limit,
+                            uint64_t cand) {
+  if (!limit || limit >= st.eligible) return false;
+  if (st.depth >= (uint32_t)kSnapOrderPasses) return false;
+  return !(cand >= 2 && st.bucket <= cand);
+}
+
+// The two rows of one gather lane (bits b, b + 1 of `tile`, whose selected
+// bitmap is `words` and exclusive offset `off`): their sort records to
+// candidate slot = rank, so candidates stand in position order.
+//   ckey[rank] = image, cval[rank] = class << 32 | position.
+DEV void snap_order_gather_pair(const SnapOrder& o, const uint64_t* words,
+                                uint64_t tile, uint64_t off, uint32_t b,
+                                uint64_t* ckey, uint64_t* cval) {
+  uint64_t w = 0;
+#pragma unroll
+  for (int i = 0; i < kSnapTileWords; ++i)
+    if ((b >> 6) == (uint32_t)i) w = words[i];
+  const uint32_t two = (uint32_t)(w >> (b & 63)) & 3u;
+  if (!two) return;
+  uint64_t rank = off + snap_select_rank(words, b);
+#pragma unroll
+  for (uint32_t j = 0; j < 2; ++j) {
+    if (!((two >> j) & 1u)) continue;
+    const uint64_t pos = tile * kSnapTileRows + b + j;
+    const uint32_t nm = o.nullmask ? o.nullmask[pos] : 0u;
+    const SnapOrderKey k =
+        snap_order_key(o, o.col[pos], (nm & o.null_m) != 0, pos);
+    ckey[rank] = k.img;
+    cval[rank] = ((uint64_t)k.cls << 32) | k.pos;
+    ++rank;
+  }
+}
+
+// The last delivered row, for the next page.
+struct SnapOrderCursor {
+  uint64_t datum, row;
+  uint32_t is_null, pad_;
+};
+
+// Delivered row idx of n from its sorted record.
+DEV void snap_order_emit(const SnapOrder& o, const SnapSelect& s,
+                         const SnapSelectOut& so, uint64_t rec, uint64_t idx,
+                         uint64_t n, SnapOrderCursor* cur) {
+  const uint64_t pos = rec & 0xffffffffull;
+  snap_select_emit(s, so, pos, idx);
+  if (idx + 1 == n) {
+    const bool nul = snap_order_is_null(o, (uint32_t)(rec >> 32));
+    cur->is_null = nul ? 1u : 0u;
+    cur->datum = nul ? 0 : o.col[pos];
+    cur->row = pos;
+    cur->pad_ = 0;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side: ABI query -> SnapQuery. Returns 0, or 9 with a message naming
 // the offending predicate / aggregate (nothing may be launched then).
 // cols == nullptr validates only (column pointers left null). IN / IN_RANGE
@@ -1138,6 +1376,102 @@ inline void snap_select_fill(uint64_t lo, uint64_t hi, const SnapSelectHdr& h,
     out->resume_row = out->done ? lo : first_pos;
   else
     out->resume_row = out->done ? hi : last_pos + 1;
+}
+
+// ABI ordered select -> SnapQuery + SnapSelect (snap_build_select's rules,
+// string projection allowed) + SnapOrder.
+inline int snap_build_order(const ybg_schema_t& sc, const SnapCols* cols,
+                            const ybg_snapshot_order_t& oq, uint64_t n_rows,
+                            std::vector<uint8_t>* aux, SnapQuery* out_q,
+                            SnapSelect* out_sel, SnapOrder* out, char* err,
+                            size_t err_cap) {
+  memset(out, 0, sizeof(*out));
+  int rc = snap_build_select(sc, cols, oq.sel, n_rows, aux, out_q, out_sel,
+                             err, err_cap, true);
+  if (rc) return rc;
+  if (oq.sel.backward) {
+    snprintf(err, err_cap,
+             "snapshot ordered select: backward %d: the direction is "
+             "`descending`, sel.backward must be 0", oq.sel.backward);
+    return 9;
+  }
+  const int nk = sc.num_hash_cols + sc.num_range_cols;
+  int dt;
+  if (oq.order_is_key_col) {
+    if (oq.order_col < 0 || oq.order_col >= nk) {
+      snprintf(err, err_cap,
+               "snapshot ordered select: order column: key column %d out of "
+               "range", oq.order_col);
+      return 9;
+    }
+    if (sc.key_types[oq.order_col] == YBG_KT_STRING) {
+      snprintf(err, err_cap,
+               "snapshot ordered select: order column: string key column %d "
+               "is not supported", oq.order_col);
+      return 9;
+    }
+    dt = YBG_T_INT64;
+    if (cols) out->col = cols->key[oq.order_col];
+  } else {
+    if (oq.order_col < 0 || oq.order_col >= sc.num_value_cols) {
+      snprintf(err, err_cap,
+               "snapshot ordered select: order column: value column %d out "
+               "of range", oq.order_col);
+      return 9;
+    }
+    dt = sc.value_cols[oq.order_col].dtype;
+    if (dt == YBG_T_STRING) {
+      snprintf(err, err_cap,
+               "snapshot ordered select: order column: string column %d is "
+               "not supported", oq.order_col);
+      return 9;
+    }
+    if (cols) out->col = cols->val[oq.order_col];
+    out->null_m = 1u << oq.order_col;
+    const uint32_t nullable = cols ? cols->nullable_cols : 0xffffffffu;
+    if (cols && (nullable & out->null_m)) out->nullmask = cols->nullmask;
+  }
+  if (oq.have_cursor && oq.cursor_row >= (1ull << 32)) {
+    snprintf(err, err_cap,
+             "snapshot ordered select: cursor_row %llu: positions are below "
+             "2^32", (unsigned long long)oq.cursor_row);
+    return 9;
+  }
+  out->kind = dt == YBG_T_DOUBLE ? kSnapOrderDouble
+              : dt == YBG_T_FLOAT ? kSnapOrderFloat : kSnapOrderInt;
+  out->descending = oq.descending ? 1 : 0;
+  out->nulls_first = oq.nulls_first ? 1 : 0;
+  out->have_cursor = oq.have_cursor ? 1 : 0;
+  if (out->have_cursor)
+    out->cursor = snap_order_key(*out, oq.cursor_datum,
+                                 oq.cursor_is_null != 0, oq.cursor_row);
+  return 0;
+}
+
+// Early-out threshold of a call: YBG_SNAP_ORDER_CAND, else the default.
+inline uint64_t snap_order_cand_env() {
+  const char* e = getenv("YBG_SNAP_ORDER_CAND");
+  if (!e || !*e) return kSnapOrderCand;
+  const unsigned long long v = strtoull(e, nullptr, 10);
+  return v ? v : kSnapOrderCand;
+}
+
+// Counters of an ordered select: n delivered of `eligible`.
+inline void snap_order_fill(uint64_t lo, uint64_t hi, uint64_t n,
+                            uint64_t eligible, uint32_t passes,
+                            const SnapOrderCursor* cur,
+                            ybg_snapshot_order_result_t* out) {
+  out->r.n_rows = n;
+  out->r.rows_scanned = hi > lo ? hi - lo : 0;
+  out->r.rows_matched = eligible;
+  out->r.done = n == eligible ? 1 : 0;
+  out->r.resume_row = 0;
+  out->digit_passes = passes;
+  if (cur && n) {
+    out->cursor_is_null = (int32_t)cur->is_null;
+    out->cursor_datum = cur->datum;
+    out->cursor_row = cur->row;
+  }
 }
 
 // Final result record of a query (k_snap_reduce output / simulator fold).

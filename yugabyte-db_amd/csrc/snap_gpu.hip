@@ -24,6 +24,13 @@
 //    key order as an ordered stream compaction in three launches (per-tile
 //    match bitmap + counts, one-workgroup prefix sum, rank and gather of the
 //    projected columns); no workgroup waits on another.
+//  * k_snap_order_hist / _fix / _mark / _gather / _emit: ORDER BY / top-N —
+//    a radix select between the select's match bitmap and its emit, over a
+//    key that cannot tie (NULL class, value image, position): per 8-bit
+//    digit a workgroup-LDS histogram flushed with integer adds and a
+//    one-workgroup prefix sum that fixes the digit of the limit-th key; the
+//    rows at or below it become a second bitmap, are compacted in position
+//    order, radix-sorted (stable) and emitted. Launch boundaries only.
 //  * strings (yb_gpu_snapshot_build_ex with stage_strings): k_emit fills a
 //    temporary heap sized by a counting emit pass; per string column
 //    k_snap_str_len / rocprim exclusive scan / k_snap_str_pack turn it into
@@ -478,6 +485,200 @@ __global__ __launch_bounds__(kSnapThreads) void k_snap_select_gather(
 }
 
 // ---------------------------------------------------------------------------
+// ORDER BY / top-N: hist / fix / mark / gather / emit (snap_device.h has the
+// key, the digit and the state logic). The tile walk is the select's:
+// workgroup w takes the window's tiles w, w + gridDim.x, ..., lane l owns
+// bits 2l and 2l + 1 of the tile's match bitmap and loads its row pair of
+// the order column with one 16-byte load, only when one of the two matched.
+// ---------------------------------------------------------------------------
+
+// One lane's share of a tile: its two match bits, and for a matched pair the
+// order datums (and null words). Matched rows lie inside the window, below
+// n_rows, so the pair load stays inside the padded column.
+template <bool NULLS>
+__device__ __forceinline__ uint32_t snap_order_load(
+    const SnapOrder& o, const unsigned long long* __restrict__ bitmap,
+    uint64_t tile, snap_u64x2* v, snap_u32x2* nm) {
+  const uint32_t b = threadIdx.x * kSnapVec;
+  const uint64_t w = bitmap[tile * kSnapTileWords + (b >> 6)];
+  const uint32_t two = (uint32_t)(w >> (b & 63)) & 3u;
+  *v = snap_u64x2{0ull, 0ull};
+  *nm = snap_u32x2{0u, 0u};
+  if (two) {
+    const uint64_t r0 = tile * kSnapTileRows + b;
+    *v = *reinterpret_cast<const snap_u64x2*>(o.col + r0);
+    if (NULLS) *nm = *reinterpret_cast<const snap_u32x2*>(o.nullmask + r0);
+  }
+  return two;
+}
+
+// One row per lane into the workgroup histogram. A column with few distinct
+// values sends the whole wave to one bin: when every counted lane holds the
+// same digit (one ballot and one compare), one lane adds the popcount
+// instead of up to 64 same-address LDS atomics being serialised.
+__device__ __forceinline__ void snap_order_hist_add(unsigned* hist, bool act,
+                                                    uint32_t digit) {
+  const uint64_t m = __ballot(act);
+  if (!m) return;  // wave-uniform
+  const int src = __ffsll((unsigned long long)m) - 1;
+  const uint32_t d0 = (uint32_t)__shfl((int)digit, src);
+  const uint64_t same = __ballot(act && digit == d0);
+  if (same == m) {
+    if ((int)(threadIdx.x & 63) == src)
+      atomicAdd(&hist[d0], (unsigned)__popcll(m));
+  } else if (act) {
+    atomicAdd(&hist[digit], 1u);
+  }
+}
+
+// Digit pass: bins[d] += matched, eligible rows of the bucket whose digit
+// `pass` is d. Tiles without a match are skipped from their count word; the
+// workgroup's LDS histogram is flushed with one global integer add per
+// non-zero bin. A workgroup counts fewer than 2^32 rows (positions are
+// 32-bit), so the LDS bins are 32-bit.
+template <bool NULLS>
+__global__ __launch_bounds__(kSnapThreads) void k_snap_order_hist(
+    SnapOrder o, SnapWindow win, int pass,
+    const SnapOrderState* __restrict__ stp,
+    const unsigned long long* __restrict__ bitmap,
+    const unsigned long long* __restrict__ tile_cnt,
+    unsigned long long* __restrict__ bins) {
+  __shared__ unsigned hist[kSnapOrderBins];
+  for (int i = threadIdx.x; i < kSnapOrderBins; i += kSnapThreads) hist[i] = 0;
+  __syncthreads();
+  const SnapOrderState st = *stp;
+  for (uint64_t t = blockIdx.x; t < win.n_tiles; t += gridDim.x) {
+    if (tile_cnt[t] == 0) continue;
+    const uint64_t tile = win.tile_lo + t;
+    snap_u64x2 v;
+    snap_u32x2 nm;
+    const uint32_t two = snap_order_load<NULLS>(o, bitmap, tile, &v, &nm);
+    const uint64_t r0 = tile * kSnapTileRows + threadIdx.x * kSnapVec;
+    SnapOrderKey k0, k1;
+    const bool a0 = snap_order_row(o, v.x, nm.x, r0, two & 1u, &k0) &&
+                    snap_order_in_bucket(k0, st);
+    const bool a1 = snap_order_row(o, v.y, nm.y, r0 + 1, (two & 2u) != 0, &k1) &&
+                    snap_order_in_bucket(k1, st);
+    snap_order_hist_add(hist, a0, snap_order_digit(k0, pass));
+    snap_order_hist_add(hist, a1, snap_order_digit(k1, pass));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kSnapOrderBins; i += kSnapThreads) {
+    const unsigned c = hist[i];
+    if (c) atomicAdd(&bins[i], (unsigned long long)c);
+  }
+}
+
+// One workgroup, one bin per thread: inclusive prefix sum of the bins
+// (doubling steps through two LDS buffers), then the one thread whose bin
+// holds the k-th key of the bucket advances the state. The bins are left
+// zeroed for the next pass. Every thread reads the state before the first
+// barrier; the state is written after the last.
+__global__ __launch_bounds__(kSnapOrderBins) void k_snap_order_fix(
+    int pass, uint64_t limit, unsigned long long* __restrict__ bins,
+    SnapOrderState* __restrict__ st) {
+  __shared__ unsigned long long sc[2][kSnapOrderBins];
+  const unsigned t = threadIdx.x;
+  const unsigned long long cnt = bins[t];
+  bins[t] = 0;
+  SnapOrderState s = *st;
+  uint64_t k = s.k;
+  sc[0][t] = cnt;
+  __syncthreads();
+  int cur = 0;
+  for (unsigned off = 1; off < (unsigned)kSnapOrderBins; off <<= 1) {
+    unsigned long long v = sc[cur][t];
+    if (t >= off) v += sc[cur][t - off];
+    sc[cur ^ 1][t] = v;
+    __syncthreads();
+    cur ^= 1;
+  }
+  const uint64_t incl = sc[cur][t], total = sc[cur][kSnapOrderBins - 1];
+  const uint64_t excl = incl - cnt;
+  if (pass == 0) {
+    if (!snap_order_begin(&s, total, limit)) {
+      if (t == 0) *st = s;
+      return;
+    }
+    k = s.k;
+  }
+  if (cnt && excl < k && k <= incl) {
+    snap_order_advance(&s, pass, t, excl, cnt);
+    *st = s;
+  }
+}
+
+// Selected rows (matched, eligible, key prefix at or below the fixed one) as
+// a second bitmap with the count pass's per-tile count words, so the
+// select's scan and rank code apply unchanged. A tile without a match gets a
+// zero count and its bitmap words are left alone (nothing reads them).
+template <bool NULLS>
+__global__ __launch_bounds__(kSnapThreads) void k_snap_order_mark(
+    SnapOrder o, SnapWindow win, const SnapOrderState* __restrict__ stp,
+    const unsigned long long* __restrict__ bitmap,
+    const unsigned long long* __restrict__ tile_cnt,
+    unsigned long long* __restrict__ sel_bitmap,
+    unsigned long long* __restrict__ sel_cnt) {
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const SnapOrderState st = *stp;
+  for (uint64_t t = blockIdx.x; t < win.n_tiles; t += gridDim.x) {
+    if (tile_cnt[t] == 0) {
+      if (lane == 0) reinterpret_cast<uint16_t*>(sel_cnt + t)[wave] = 0;
+      continue;
+    }
+    const uint64_t tile = win.tile_lo + t;
+    snap_u64x2 v;
+    snap_u32x2 nm;
+    const uint32_t two = snap_order_load<NULLS>(o, bitmap, tile, &v, &nm);
+    const uint64_t r0 = tile * kSnapTileRows + threadIdx.x * kSnapVec;
+    SnapOrderKey k0, k1;
+    const bool s0 = snap_order_row(o, v.x, nm.x, r0, two & 1u, &k0) &&
+                    snap_order_selected(k0, st);
+    const bool s1 = snap_order_row(o, v.y, nm.y, r0 + 1, (two & 2u) != 0, &k1) &&
+                    snap_order_selected(k1, st);
+    const uint64_t b0 = __ballot(s0), b1 = __ballot(s1);
+    if (lane == 0) {
+      uint64_t w[2];
+      snap_select_pack(b0, b1, w);
+      *reinterpret_cast<snap_u64x2*>(sel_bitmap + tile * kSnapTileWords +
+                                     wave * 2) = snap_u64x2{w[0], w[1]};
+      reinterpret_cast<uint16_t*>(sel_cnt + t)[wave] =
+          (uint16_t)(__popcll(b0) + __popcll(b1));
+    }
+  }
+}
+
+// The selected rows' sort records in position order (slot = tile offset +
+// rank inside the tile), from the selected bitmap alone plus one column read
+// per selected row.
+__global__ __launch_bounds__(kSnapThreads) void k_snap_order_gather(
+    SnapOrder o, SnapWindow win,
+    const unsigned long long* __restrict__ sel_bitmap,
+    const unsigned long long* __restrict__ sel_cnt,
+    const uint32_t* __restrict__ tile_off, uint64_t* __restrict__ ckey,
+    uint64_t* __restrict__ cval) {
+  for (uint64_t t = blockIdx.x; t < win.n_tiles; t += gridDim.x) {
+    if (snap_select_tile_count(sel_cnt[t]) == 0) continue;
+    const uint64_t tile = win.tile_lo + t;
+    uint64_t words[kSnapTileWords];
+#pragma unroll
+    for (int w = 0; w < kSnapTileWords; ++w)
+      words[w] = sel_bitmap[tile * kSnapTileWords + w];
+    snap_order_gather_pair(o, words, tile, tile_off[t],
+                           threadIdx.x * kSnapVec, ckey, cval);
+  }
+}
+
+// Delivered row i = sorted record i, for the first n records.
+__global__ __launch_bounds__(256) void k_snap_order_emit(
+    SnapOrder o, SnapSelect s, SnapSelectOut so,
+    const uint64_t* __restrict__ recs, uint64_t n,
+    SnapOrderCursor* __restrict__ cur) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) snap_order_emit(o, s, so, recs[i], i, n, cur);
+}
+
+// ---------------------------------------------------------------------------
 // Build kernels
 // ---------------------------------------------------------------------------
 
@@ -660,6 +861,20 @@ struct ybg_snapshot {
   size_t sel_scan_bytes = 0;
   uint8_t* d_sel_heap = nullptr;
   uint64_t sel_heap_cap = 0;
+  // ordered select: the selected bitmap, its tile counts, the digit bins,
+  // the selection state and the out-cursor, allocated by the first ordered
+  // select; the candidate records (two key and two value arrays of ord_cap
+  // entries) and the sort's temporary storage, grown on demand
+  unsigned long long* d_ord_bitmap = nullptr;  // [tiles * kSnapTileWords]
+  unsigned long long* d_ord_cnt = nullptr;     // [snap_select_tile_slots]
+  unsigned long long* d_ord_bins = nullptr;    // [kSnapOrderBins]
+  SnapOrderState* d_ord_state = nullptr;
+  SnapOrderCursor* d_ord_cursor = nullptr;
+  uint64_t* d_ord_key[2] = {nullptr, nullptr};
+  uint64_t* d_ord_val[2] = {nullptr, nullptr};
+  uint64_t ord_cap = 0;
+  void* d_ord_sort = nullptr;
+  size_t ord_sort_bytes = 0;
 };
 
 namespace {
@@ -697,6 +912,12 @@ void snap_free(ybg_snapshot* sn) {
   void* select_var[] = {sn->d_sel_strlen, sn->d_sel_stroff, sn->d_sel_scan,
                         sn->d_sel_heap};
   for (void* p : select_var)
+    if (p) HIP_WARN(hipFree(p));
+  void* ordered[] = {sn->d_ord_bitmap, sn->d_ord_cnt, sn->d_ord_bins,
+                     sn->d_ord_state, sn->d_ord_cursor, sn->d_ord_key[0],
+                     sn->d_ord_key[1], sn->d_ord_val[0], sn->d_ord_val[1],
+                     sn->d_ord_sort};
+  for (void* p : ordered)
     if (p) HIP_WARN(hipFree(p));
   if (sn->ev_s0) HIP_WARN(hipEventDestroy(sn->ev_s0));
   if (sn->ev_s1) HIP_WARN(hipEventDestroy(sn->ev_s1));
@@ -1150,6 +1371,58 @@ int snap_select_ensure_heap(ybg_snapshot* sn, uint64_t bytes) {
   return 0;
 }
 
+// String projection of n delivered rows (so.row_ids / datums written):
+// per-row byte counts -> exclusive scan -> row offsets; the total sizes the
+// heap, its copy and the varlen_cap check. *heap_bytes = bytes needed; the
+// copy into sn->d_sel_heap is launched only when they fit varlen_cap.
+int snap_select_strings(ybg_snapshot* sn, const SnapSelect& sel,
+                        const SnapSelectOut& so, uint64_t n,
+                        uint64_t varlen_cap, uint64_t* heap_bytes) {
+  int rc = 0;
+  const int sgrid = (int)((n + 1 + 255) / 256);
+  size_t need = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, need, sn->d_sel_strlen,
+                                  sn->d_sel_stroff, (uint64_t)0,
+                                  (size_t)(n + 1),
+                                  rocprim::plus<uint64_t>(), sn->stream));
+  if ((rc = snap_select_ensure_str(sn, n, need))) return rc;
+  hipLaunchKernelGGL(k_snap_select_strlen, dim3(sgrid), dim3(256), 0,
+                     sn->stream, sel, so, n, sn->d_sel_strlen);
+  HIP_TRY(rocprim::exclusive_scan(sn->d_sel_scan, need, sn->d_sel_strlen,
+                                  sn->d_sel_stroff, (uint64_t)0,
+                                  (size_t)(n + 1),
+                                  rocprim::plus<uint64_t>(), sn->stream));
+  HIP_TRY(hipMemcpyAsync(heap_bytes, sn->d_sel_stroff + n, 8,
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  if (*heap_bytes > varlen_cap) return 0;
+  if ((rc = snap_select_ensure_heap(sn, *heap_bytes))) return rc;
+  hipLaunchKernelGGL(k_snap_select_strcopy, dim3(sgrid), dim3(256), 0,
+                     sn->stream, sel, so, n, sn->d_sel_stroff,
+                     sn->d_sel_heap);
+  return 0;
+}
+
+// The count pass of a select: the instantiation the query needs.
+void snap_select_count_dispatch(ybg_snapshot* sn, const SnapQuery& q,
+                                const SnapWindow& win, int grid) {
+  if (q.general == kSnapGenStr)
+    snap_select_launch_count<8, kSnapGenStr>(q, win, grid, sn->stream,
+                                             sn->d_sel_bitmap, sn->d_sel_cnt);
+  else if (q.general)
+    snap_select_launch_count<8, kSnapGenList>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
+  else if (q.num_preds <= 4)
+    snap_select_launch_count<4, kSnapGenFast>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
+  else
+    snap_select_launch_count<8, kSnapGenFast>(q, win, grid, sn->stream,
+                                              sn->d_sel_bitmap,
+                                              sn->d_sel_cnt);
+}
+
 // varlen_size == nullptr: yb_gpu_snapshot_select (no string projection);
 // otherwise yb_gpu_snapshot_select_var.
 int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
@@ -1186,21 +1459,7 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
   const int grid =
       (int)(win.n_tiles < kSnapMaxGrid ? win.n_tiles : kSnapMaxGrid);
   HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
-  if (q.general == kSnapGenStr)
-    snap_select_launch_count<8, kSnapGenStr>(q, win, grid, sn->stream,
-                                             sn->d_sel_bitmap, sn->d_sel_cnt);
-  else if (q.general)
-    snap_select_launch_count<8, kSnapGenList>(q, win, grid, sn->stream,
-                                              sn->d_sel_bitmap,
-                                              sn->d_sel_cnt);
-  else if (q.num_preds <= 4)
-    snap_select_launch_count<4, kSnapGenFast>(q, win, grid, sn->stream,
-                                              sn->d_sel_bitmap,
-                                              sn->d_sel_cnt);
-  else
-    snap_select_launch_count<8, kSnapGenFast>(q, win, grid, sn->stream,
-                                              sn->d_sel_bitmap,
-                                              sn->d_sel_cnt);
+  snap_select_count_dispatch(sn, q, win, grid);
   hipLaunchKernelGGL(k_snap_select_scan, dim3(1), dim3(kSnapScanThreads), 0,
                      sn->stream, sn->d_sel_cnt, sn->d_sel_off, win.n_tiles,
                      snap_select_tile_slots(win.n_tiles), sq->row_limit,
@@ -1235,24 +1494,8 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
                      sn->d_sel_cnt, sn->d_sel_off, sn->d_sel_hdr);
   uint64_t heap_bytes = 0;
   if (sel.num_str) {
-    // per-row byte counts -> exclusive scan -> row offsets; the total sizes
-    // the heap, its copy and the varlen_cap check
-    const int sgrid = (int)((n + 1 + 255) / 256);
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, sn->d_sel_strlen,
-                                    sn->d_sel_stroff, (uint64_t)0,
-                                    (size_t)(n + 1),
-                                    rocprim::plus<uint64_t>(), sn->stream));
-    if ((rc = snap_select_ensure_str(sn, n, need))) return rc;
-    hipLaunchKernelGGL(k_snap_select_strlen, dim3(sgrid), dim3(256), 0,
-                       sn->stream, sel, so, n, sn->d_sel_strlen);
-    HIP_TRY(rocprim::exclusive_scan(sn->d_sel_scan, need, sn->d_sel_strlen,
-                                    sn->d_sel_stroff, (uint64_t)0,
-                                    (size_t)(n + 1),
-                                    rocprim::plus<uint64_t>(), sn->stream));
-    HIP_TRY(hipMemcpyAsync(&heap_bytes, sn->d_sel_stroff + n, 8,
-                           hipMemcpyDeviceToHost, sn->stream));
-    HIP_TRY(hipStreamSynchronize(sn->stream));
+    if ((rc = snap_select_strings(sn, sel, so, n, varlen_cap, &heap_bytes)))
+      return rc;
     *varlen_size = heap_bytes;
     if (heap_bytes > varlen_cap) {
       snap_select_fill(lo, hi, h, sel.backward, 0, 0, out);
@@ -1262,10 +1505,6 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
                             " string bytes exceed the varlen capacity " +
                             std::to_string(varlen_cap));
     }
-    if ((rc = snap_select_ensure_heap(sn, heap_bytes))) return rc;
-    hipLaunchKernelGGL(k_snap_select_strcopy, dim3(sgrid), dim3(256), 0,
-                       sn->stream, sel, so, n, sn->d_sel_stroff,
-                       sn->d_sel_heap);
   }
   HIP_TRY(hipEventRecord(sn->ev_s1, sn->stream));
   if (heap_bytes)
@@ -1284,6 +1523,273 @@ int snap_select(ybg_snapshot* sn, const ybg_snapshot_select_t* sq,
   sn->last_query_ms = (double)ms + ms2;
   snap_select_fill(lo, hi, h, sel.backward, row_ids[n - 1], row_ids[n - 1],
                    out);
+  return 0;
+}
+
+// ---- ordered select ---------------------------------------------------------
+
+// First ordered select: the selected bitmap, its counts, bins, state, cursor.
+int snap_order_ensure_scratch(ybg_snapshot* sn) {
+  const uint64_t tiles = (sn->n_rows + kSnapTileRows - 1) / kSnapTileRows;
+  const uint64_t slots = snap_select_tile_slots(tiles);
+  int rc = 0;
+  if ((rc = snap_group_alloc(sn, &sn->d_ord_bitmap,
+                             tiles * kSnapTileWords * 8)))
+    return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_ord_cnt, slots * 8))) return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_ord_bins, kSnapOrderBins * 8)))
+    return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_ord_state, sizeof(SnapOrderState))))
+    return rc;
+  if ((rc = snap_group_alloc(sn, &sn->d_ord_cursor, sizeof(SnapOrderCursor))))
+    return rc;
+  return 0;
+}
+
+// Candidate records for c selected rows and the sort's temporary storage.
+int snap_order_ensure_cand(ybg_snapshot* sn, uint64_t c, size_t sort_need) {
+  int rc = 0;
+  if (c > sn->ord_cap) {
+    for (int i = 0; i < 2; ++i) {
+      if (sn->d_ord_key[i]) HIP_WARN(hipFree(sn->d_ord_key[i]));
+      if (sn->d_ord_val[i]) HIP_WARN(hipFree(sn->d_ord_val[i]));
+      sn->d_ord_key[i] = sn->d_ord_val[i] = nullptr;
+    }
+    sn->device_bytes -= sn->ord_cap * 8 * 4;
+    sn->ord_cap = 0;
+    uint64_t want = 1024;
+    while (want < c) want <<= 1;
+    for (int i = 0; i < 2; ++i) {
+      if ((rc = snap_group_alloc(sn, &sn->d_ord_key[i], want * 8))) return rc;
+      if ((rc = snap_group_alloc(sn, &sn->d_ord_val[i], want * 8))) return rc;
+    }
+    sn->ord_cap = want;
+  }
+  if (sort_need > sn->ord_sort_bytes) {
+    if (sn->d_ord_sort) HIP_WARN(hipFree(sn->d_ord_sort));
+    sn->d_ord_sort = nullptr;
+    sn->device_bytes -= sn->ord_sort_bytes;
+    sn->ord_sort_bytes = 0;
+    if ((rc = snap_group_alloc(sn, &sn->d_ord_sort, sort_need))) return rc;
+    sn->ord_sort_bytes = sort_need;
+  }
+  return 0;
+}
+
+template <bool NULLS>
+void snap_order_launch_hist(ybg_snapshot* sn, const SnapOrder& o,
+                            const SnapWindow& win, int grid, int pass) {
+  hipLaunchKernelGGL((k_snap_order_hist<NULLS>), dim3(grid),
+                     dim3(kSnapThreads), 0, sn->stream, o, win, pass,
+                     sn->d_ord_state, sn->d_sel_bitmap, sn->d_sel_cnt,
+                     sn->d_ord_bins);
+}
+
+template <bool NULLS>
+void snap_order_launch_mark(ybg_snapshot* sn, const SnapOrder& o,
+                            const SnapWindow& win, int grid) {
+  hipLaunchKernelGGL((k_snap_order_mark<NULLS>), dim3(grid),
+                     dim3(kSnapThreads), 0, sn->stream, o, win,
+                     sn->d_ord_state, sn->d_sel_bitmap, sn->d_sel_cnt,
+                     sn->d_ord_bitmap, sn->d_ord_cnt);
+}
+
+// Launch order of one call (every arrow a launch boundary, "|" a point where
+// the host reads a small header):
+//   count -> [cursor: mark] -> scan | E eligible rows
+//   [limit < E: (hist -> fix |) per digit pass -> mark -> scan |]
+//   gather -> sort (-> class sort) -> emit [-> strlen -> scan | strcopy]
+int snap_select_ordered(ybg_snapshot* sn, const ybg_snapshot_order_t* oq,
+                        uint64_t* datums, uint32_t* null_masks,
+                        uint64_t* row_ids, uint64_t cap, uint8_t* varlen,
+                        uint64_t varlen_cap, uint64_t* varlen_size,
+                        ybg_snapshot_order_result_t* out) {
+  memset(out, 0, sizeof(*out));
+  uint64_t vs_local = 0;
+  if (!varlen_size) varlen_size = &vs_local;
+  *varlen_size = 0;
+  const SnapCols cols = snap_cols(sn);
+  SnapQuery q;
+  SnapSelect sel;
+  SnapOrder ord;
+  char err[192];
+  // a launched plain query may still read aux_host / d_aux
+  if (sn->pending) HIP_TRY(hipStreamSynchronize(sn->stream));
+  sn->aux_host.clear();
+  int rc = snap_build_order(sn->schema, &cols, *oq, sn->n_rows,
+                            &sn->aux_host, &q, &sel, &ord, err, sizeof(err));
+  if (rc) return set_err(rc, err);
+  out->r.entries_seen = sn->entries_seen;
+  memcpy(out->r.restart_ht, sn->restart_ht, sn->restart_len);
+  out->r.restart_ht_len = sn->restart_len;
+  sn->last_query_ms = 0;
+  const uint64_t hi = oq->sel.row_hi < sn->n_rows ? oq->sel.row_hi : sn->n_rows;
+  const uint64_t lo = oq->sel.row_lo;
+  if (lo >= hi) {  // empty snapshot or window: nothing launched
+    snap_order_fill(lo, hi, 0, 0, 0, nullptr, out);
+    return 0;
+  }
+  const uint64_t limit = oq->sel.row_limit;
+  const uint64_t cand = snap_order_cand_env();
+  if ((rc = snap_select_ensure_scratch(sn))) return rc;
+  if ((rc = snap_order_ensure_scratch(sn))) return rc;
+  if ((rc = snap_upload_aux(sn, &q))) return rc;
+  const SnapWindow win = snap_select_window(lo, hi);
+  const uint64_t slots = snap_select_tile_slots(win.n_tiles);
+  const int grid =
+      (int)(win.n_tiles < kSnapMaxGrid ? win.n_tiles : kSnapMaxGrid);
+  const bool nulls = ord.nullmask != nullptr;
+  double total_ms = 0;
+  // end of a launch segment: the host waits and adds the segment's time
+  auto segment_end = [&](hipEvent_t e0, hipEvent_t e1) -> int {
+    HIP_TRY(hipEventRecord(e1, sn->stream));
+    HIP_TRY(hipStreamSynchronize(sn->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    total_ms += ms;
+    sn->last_query_ms = total_ms;
+    return 0;
+  };
+  auto mark_and_scan = [&]() {
+    if (nulls) snap_order_launch_mark<true>(sn, ord, win, grid);
+    else snap_order_launch_mark<false>(sn, ord, win, grid);
+    hipLaunchKernelGGL(k_snap_select_scan, dim3(1), dim3(kSnapScanThreads), 0,
+                       sn->stream, sn->d_ord_cnt, sn->d_sel_off, win.n_tiles,
+                       slots, (uint64_t)0, 0, sn->d_sel_hdr);
+  };
+
+  // eligible rows: the matches, or with a cursor the matches after it
+  SnapSelectHdr h = {0, 0, 0};
+  HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+  HIP_TRY(hipMemsetAsync(sn->d_ord_state, 0, sizeof(SnapOrderState),
+                         sn->stream));
+  HIP_TRY(hipMemsetAsync(sn->d_ord_bins, 0, kSnapOrderBins * 8, sn->stream));
+  snap_select_count_dispatch(sn, q, win, grid);
+  bool marked = ord.have_cursor != 0;
+  if (marked)
+    mark_and_scan();
+  else
+    hipLaunchKernelGGL(k_snap_select_scan, dim3(1), dim3(kSnapScanThreads), 0,
+                       sn->stream, sn->d_sel_cnt, sn->d_sel_off, win.n_tiles,
+                       slots, (uint64_t)0, 0, sn->d_sel_hdr);
+  HIP_TRY(hipMemcpyAsync(&h, sn->d_sel_hdr, sizeof(h), hipMemcpyDeviceToHost,
+                         sn->stream));
+  if ((rc = segment_end(sn->ev_q0, sn->ev_q1))) return rc;
+  const uint64_t eligible = h.total;
+  const uint64_t n = (limit && limit < eligible) ? limit : eligible;
+  if (n > cap) {
+    snap_order_fill(lo, hi, n, eligible, 0, nullptr, out);
+    out->r.done = 0;
+    return set_err(8, "snapshot ordered select: " + std::to_string(n) +
+                          " rows exceed the output capacity " +
+                          std::to_string(cap));
+  }
+  if (n == 0) {
+    snap_order_fill(lo, hi, 0, 0, 0, nullptr, out);
+    return 0;
+  }
+
+  // radix select of the n-th key, then the selected bitmap
+  uint32_t passes = 0;
+  if (n < eligible) {
+    SnapOrderState st;
+    memset(&st, 0, sizeof(st));
+    for (int pass = 0; pass < kSnapOrderPasses; ++pass) {
+      HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+      if (nulls) snap_order_launch_hist<true>(sn, ord, win, grid, pass);
+      else snap_order_launch_hist<false>(sn, ord, win, grid, pass);
+      hipLaunchKernelGGL(k_snap_order_fix, dim3(1), dim3(kSnapOrderBins), 0,
+                         sn->stream, pass, limit, sn->d_ord_bins,
+                         sn->d_ord_state);
+      HIP_TRY(hipMemcpyAsync(&st, sn->d_ord_state, sizeof(st),
+                             hipMemcpyDeviceToHost, sn->stream));
+      if ((rc = segment_end(sn->ev_q0, sn->ev_q1))) return rc;
+      ++passes;
+      if (!snap_order_more(st, limit, cand)) break;
+    }
+    HIP_TRY(hipEventRecord(sn->ev_q0, sn->stream));
+    mark_and_scan();
+    marked = true;
+    HIP_TRY(hipMemcpyAsync(&h, sn->d_sel_hdr, sizeof(h),
+                           hipMemcpyDeviceToHost, sn->stream));
+    if ((rc = segment_end(sn->ev_q0, sn->ev_q1))) return rc;
+  }
+  const uint64_t c = h.total;  // selected rows, >= n
+  if (c < n)
+    return set_err(10, "snapshot ordered select: " + std::to_string(c) +
+                           " selected rows for " + std::to_string(n));
+
+  // gather the records, sort, emit
+  size_t need = 0, need2 = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, sn->d_ord_key[0],
+                                    sn->d_ord_key[1], sn->d_ord_val[0],
+                                    sn->d_ord_val[1], (size_t)c, 0u, 64u,
+                                    sn->stream));
+  if (nulls)
+    HIP_TRY(rocprim::radix_sort_keys(nullptr, need2, sn->d_ord_val[1],
+                                     sn->d_ord_val[0], (size_t)c, 32u, 33u,
+                                     sn->stream));
+  if ((rc = snap_order_ensure_cand(sn, c, need > need2 ? need : need2)))
+    return rc;
+  if ((rc = snap_select_ensure_out(sn, n, (uint64_t)sel.num_cols))) return rc;
+  const SnapSelectOut so = {sn->d_sel_rowids, sn->d_sel_nulls,
+                            sn->d_sel_datums, sn->sel_cap};
+  HIP_TRY(hipEventRecord(sn->ev_s0, sn->stream));
+  hipLaunchKernelGGL(k_snap_order_gather, dim3(grid), dim3(kSnapThreads), 0,
+                     sn->stream, ord, win,
+                     marked ? sn->d_ord_bitmap : sn->d_sel_bitmap,
+                     marked ? sn->d_ord_cnt : sn->d_sel_cnt, sn->d_sel_off,
+                     sn->d_ord_key[0], sn->d_ord_val[0]);
+  // stable: equal images keep the gather's position order
+  HIP_TRY(rocprim::radix_sort_pairs(sn->d_ord_sort, need, sn->d_ord_key[0],
+                                    sn->d_ord_key[1], sn->d_ord_val[0],
+                                    sn->d_ord_val[1], (size_t)c, 0u, 64u,
+                                    sn->stream));
+  const uint64_t* recs = sn->d_ord_val[1];
+  if (nulls) {
+    // the NULL class on top, one more stable pass: the NULL rows become a
+    // segment of their own, before or after the values, in position order
+    HIP_TRY(rocprim::radix_sort_keys(sn->d_ord_sort, need2, sn->d_ord_val[1],
+                                     sn->d_ord_val[0], (size_t)c, 32u, 33u,
+                                     sn->stream));
+    recs = sn->d_ord_val[0];
+  }
+  hipLaunchKernelGGL(k_snap_order_emit, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, sn->stream, ord, sel, so, recs, n,
+                     sn->d_ord_cursor);
+  uint64_t heap_bytes = 0;
+  if (sel.num_str) {
+    if ((rc = snap_select_strings(sn, sel, so, n, varlen_cap, &heap_bytes)))
+      return rc;
+    *varlen_size = heap_bytes;
+    if (heap_bytes > varlen_cap) {
+      snap_order_fill(lo, hi, n, eligible, passes, nullptr, out);
+      out->r.done = 0;
+      return set_err(8, "snapshot ordered select: " +
+                            std::to_string(heap_bytes) +
+                            " string bytes exceed the varlen capacity " +
+                            std::to_string(varlen_cap));
+    }
+  }
+  SnapOrderCursor cur;
+  HIP_TRY(hipEventRecord(sn->ev_s1, sn->stream));
+  if (heap_bytes)
+    HIP_TRY(hipMemcpyAsync(varlen, sn->d_sel_heap, heap_bytes,
+                           hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipMemcpyAsync(&cur, sn->d_ord_cursor, sizeof(cur),
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipMemcpyAsync(row_ids, sn->d_sel_rowids, n * 8,
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipMemcpyAsync(null_masks, sn->d_sel_nulls, n * 4,
+                         hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipMemcpy2DAsync(datums, cap * 8, sn->d_sel_datums,
+                           sn->sel_cap * 8, n * 8, (size_t)sel.num_cols,
+                           hipMemcpyDeviceToHost, sn->stream));
+  HIP_TRY(hipStreamSynchronize(sn->stream));
+  float ms_tail = 0;
+  HIP_TRY(hipEventElapsedTime(&ms_tail, sn->ev_s0, sn->ev_s1));
+  sn->last_query_ms = total_ms + ms_tail;
+  snap_order_fill(lo, hi, n, eligible, passes, &cur, out);
   return 0;
 }
 
@@ -1705,6 +2211,19 @@ int yb_gpu_snapshot_select_var(ybg_snapshot_t* sn,
 }
 
 uint64_t ybg_snapshot_select_tile_rows(void) { return kSnapTileRows; }
+
+int yb_gpu_snapshot_select_ordered(ybg_snapshot_t* sn,
+                                   const ybg_snapshot_order_t* q,
+                                   uint64_t* datums, uint32_t* null_masks,
+                                   uint64_t* row_ids, uint64_t cap,
+                                   uint8_t* varlen, uint64_t varlen_cap,
+                                   uint64_t* varlen_size,
+                                   ybg_snapshot_order_result_t* out) {
+  return snap_select_ordered(sn, q, datums, null_masks, row_ids, cap, varlen,
+                             varlen_cap, varlen_size, out);
+}
+
+uint64_t ybg_snapshot_order_candidate_rows(void) { return kSnapOrderCand; }
 
 uint64_t ybg_snapshot_group_local_slots(int32_t num_aggs) {
   return (uint64_t)snap_group_local_slots(snap_group_na(num_aggs));

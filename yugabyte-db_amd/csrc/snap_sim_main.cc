@@ -17,9 +17,14 @@
 // string EQ, a tie-breaking LT, a key IN and a select_var (forward, backward
 // with a limit, varlen capacity one byte short), cross-checked against the
 // block-path simulator and the rows the driver wrote.
+// The ordered select runs over the edge table too: ordered by the nullable
+// double column, ASC and DESC, unlimited, limited and behind a cursor, with
+// the early-out at its default and switched off (YBG_SNAP_ORDER_CAND=1),
+// cross-checked against the key-order select stable-sorted by the driver.
 // TEST INFRASTRUCTURE; not linked into the product library.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -62,6 +67,10 @@ extern "C" int ybg_sim_snapshot_select_var(
     const ybg_scan_spec_t*, const uint8_t*, const uint64_t*, uint64_t,
     const ybg_snapshot_select_t*, int, uint64_t*, uint32_t*, uint64_t*,
     uint64_t, uint8_t*, uint64_t, uint64_t*, ybg_snapshot_select_result_t*);
+extern "C" int ybg_sim_snapshot_select_ordered(
+    const ybg_scan_spec_t*, const uint8_t*, const uint64_t*, uint64_t,
+    const ybg_snapshot_order_t*, int, uint64_t*, uint32_t*, uint64_t*,
+    uint64_t, uint8_t*, uint64_t, uint64_t*, ybg_snapshot_order_result_t*);
 
 namespace {
 
@@ -255,6 +264,101 @@ int check_select(ybg_scan_spec_t spec, const uint8_t* data,
   return bad;
 }
 
+// The ordered select over (the tablet, q's predicates), ordered by the
+// nullable double column, ASC and DESC, NULLs last: unlimited, the first 5,
+// and the page behind that page's cursor, each under the default early-out
+// and at full depth (YBG_SNAP_ORDER_CAND=1). Expected: the key-order select
+// of the same simulator, stable-sorted here.
+int check_ordered(const ybg_scan_spec_t& bs, const uint8_t* data,
+                  const uint64_t* offsets, uint64_t n_blocks, uint64_t n,
+                  const ybg_snapshot_query_t& q) {
+  ybg_snapshot_order_t oq;
+  memset(&oq, 0, sizeof(oq));
+  oq.sel.num_preds = q.num_preds;
+  memcpy(oq.sel.preds, q.preds, sizeof(oq.sel.preds));
+  oq.sel.num_cols = 2;
+  oq.sel.cols[0] = {1, 0};
+  oq.sel.cols[1] = {0, 1};
+  oq.sel.row_hi = UINT64_MAX;
+  oq.order_col = 1;
+  const uint64_t cap = n + 1;
+  std::vector<uint64_t> base(cap * 2), base_ids(cap), datums(cap * 2),
+      ids(cap);
+  std::vector<uint32_t> base_nm(cap), nms(cap);
+  ybg_snapshot_select_result_t sres;
+  int bad = ybg_sim_snapshot_select(&bs, data, offsets, n_blocks, &oq.sel,
+                                    base.data(), base_nm.data(),
+                                    base_ids.data(), cap, &sres);
+  if (bad) return bad;
+  int calls = 0;
+  for (int desc = 0; desc < 2; ++desc) {
+    std::vector<uint64_t> order(sres.n_rows);
+    for (uint64_t i = 0; i < sres.n_rows; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+      const bool na = base_nm[a] & 2u, nb = base_nm[b] & 2u;
+      if (na != nb) return nb;  // NULLs last
+      if (na) return false;
+      double da, db;
+      memcpy(&da, &base[cap + a], 8);
+      memcpy(&db, &base[cap + b], 8);
+      return desc ? da > db : da < db;
+    });
+    oq.descending = desc;
+    for (const char* cand : {"", "1"}) {
+      if (*cand) setenv("YBG_SNAP_ORDER_CAND", cand, 1);
+      else unsetenv("YBG_SNAP_ORDER_CAND");
+      struct Page { uint64_t start, limit; };
+      const Page pages[] = {{0, 0}, {0, 5}, {5, 5}, {5, 0}};
+      for (const Page& p : pages) {
+        if (p.start > order.size()) continue;
+        oq.sel.row_limit = p.limit;
+        oq.have_cursor = p.start ? 1 : 0;
+        if (p.start) {
+          const uint64_t c = order[p.start - 1];
+          oq.cursor_is_null = (base_nm[c] & 2u) ? 1 : 0;
+          oq.cursor_datum = base[cap + c];
+          oq.cursor_row = base_ids[c];
+        }
+        uint64_t want = order.size() - p.start;
+        if (p.limit && p.limit < want) want = p.limit;
+        ybg_snapshot_order_result_t res;
+        uint64_t vs = 0;
+        int rc = ybg_sim_snapshot_select_ordered(
+            &bs, data, offsets, n_blocks, &oq, 0, datums.data(), nms.data(),
+            ids.data(), cap, nullptr, 0, &vs, &res);
+        const bool selects = p.limit && p.limit < order.size() - p.start;
+        int lbad = rc || res.r.n_rows != want ||
+                   res.r.rows_matched != order.size() - p.start ||
+                   res.r.done != (p.start + want == order.size() ? 1 : 0) ||
+                   (res.digit_passes != 0) != selects ||
+                   (selects && *cand && res.digit_passes != 12);
+        for (uint64_t i = 0; i < want && !lbad; ++i) {
+          const uint64_t w = order[p.start + i];
+          lbad = ids[i] != base_ids[w] || nms[i] != base_nm[w] ||
+                 datums[i] != base[w] || datums[cap + i] != base[cap + w];
+        }
+        if (!lbad && want) {
+          const uint64_t w = order[p.start + want - 1];
+          lbad = res.cursor_row != base_ids[w] ||
+                 res.cursor_datum != base[cap + w] ||
+                 res.cursor_is_null != ((base_nm[w] & 2u) ? 1 : 0);
+        }
+        if (lbad)
+          printf("  ordered desc=%d cand='%s' start=%llu limit=%llu: "
+                 "rows=%llu passes=%u MISMATCH\n", desc, cand,
+                 (unsigned long long)p.start, (unsigned long long)p.limit,
+                 (unsigned long long)res.r.n_rows, res.digit_passes);
+        bad |= lbad;
+        ++calls;
+      }
+    }
+  }
+  unsetenv("YBG_SNAP_ORDER_CAND");
+  printf("  ordered: %d calls over %llu matching rows %s\n", calls,
+         (unsigned long long)sres.n_rows, bad ? "MISMATCH" : "ok");
+  return bad;
+}
+
 int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
               const ybg_snapshot_query_t& q, bool nulls) {
   ybg_builder_t* b =
@@ -309,6 +413,10 @@ int check_one(const ybg_schema_t& schema, uint64_t n, uint64_t read_micros,
          (unsigned long long)snap.rows_matched, bad ? "MISMATCH" : "ok");
   bad |= check_grouped(spec, data, offsets, n_blocks, q);
   bad |= check_select(spec, data, offsets, n_blocks, n, q);
+  ybg_scan_spec_t bs = spec;  // the snapshot build ignores all of these
+  bs.num_preds = 0;
+  bs.num_aggs = 0;
+  bad |= check_ordered(bs, data, offsets, n_blocks, n, q);
   ybg_builder_destroy(b);
   return bad;
 }
