@@ -11,37 +11,11 @@ import struct
 import pytest
 
 import ybgpu as y
+from codec_cases import _crc32c, _mask
 
 MAGIC = 0x88E241B785F4CFF7
 FOOTER_LEN = 53
 TRAILER_LEN = 5
-
-
-def _crc32c(data, crc=0):
-    # Castagnoli, reflected poly 0x82F63B78 — bytewise, independent of the
-    # C++ implementation under test
-    tab = _crc32c.tab
-    c = crc ^ 0xFFFFFFFF
-    for b in data:
-        c = tab[(c ^ b) & 0xFF] ^ (c >> 8)
-    return c ^ 0xFFFFFFFF
-
-
-def _mk_tab():
-    tab = []
-    for i in range(256):
-        c = i
-        for _ in range(8):
-            c = (0x82F63B78 ^ (c >> 1)) if (c & 1) else (c >> 1)
-        tab.append(c)
-    return tab
-
-
-_crc32c.tab = _mk_tab()
-
-
-def _mask(crc):
-    return (((crc >> 15) | (crc << 17)) + 0xA282EAD8) & 0xFFFFFFFF
 
 
 def _build(rows=4000):

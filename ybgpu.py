@@ -347,7 +347,7 @@ class Builder:
     def finish_sst(self, compression=0):
         """Finish as a complete BlockBasedTable SST file; returns
         (data_ptr, total_bytes, n_blocks, n_entries). compression: 0 none,
-        1 snappy (blocks that do not shrink stay uncompressed)."""
+        1 snappy, 4 = LZ4 (blocks that do not shrink stay uncompressed)."""
         lib = product()
         f = _sig(lib, "ybg_builder_finish_sst2", C.c_int,
                  [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_uint8)),
@@ -1373,15 +1373,31 @@ def snappy_compress(data):
     return bytes(dst[:n])
 
 
-def snappy_uncompress(data, cap):
+_GUARD = 64
+
+
+def _uncompress_guarded(f, data, cap, guard):
+    """Call a host decompressor with capacity cap. With guard, the
+    destination is followed by 64 bytes of 0xA5 that must come back
+    unchanged: a decoder that writes past its capacity trips the assert."""
+    src = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    dst = (C.c_uint8 * (cap + (_GUARD if guard else 0)))()
+    if guard:
+        C.memset(C.byref(dst, cap), 0xA5, _GUARD)
+    n = f(src, len(data), dst, cap)
+    if guard:
+        assert bytes(dst[cap:]) == b"\xa5" * _GUARD, \
+            "decompressor wrote past its capacity"
+    return n, dst
+
+
+def snappy_uncompress(data, cap, guard=False):
     """Host snappy decompressor (same code the GPU kernel runs)."""
     lib = product()
     f = _sig(lib, "ybg_snappy_uncompress", C.c_int64,
              [C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint8),
               C.c_uint64])
-    src = (C.c_uint8 * len(data)).from_buffer_copy(data)
-    dst = (C.c_uint8 * cap)()
-    n = f(src, len(data), dst, cap)
+    n, dst = _uncompress_guarded(f, data, cap, guard)
     if n < 0:
         raise RuntimeError("snappy_uncompress failed")
     return bytes(dst[:n])
@@ -1611,15 +1627,13 @@ def lz4_compress(data):
 
 
 
-def lz4_uncompress(data, cap):
+def lz4_uncompress(data, cap, guard=False):
     """Host lz4 decompressor (same code the GPU kernel runs)."""
     lib = product()
     f = _sig(lib, "ybg_lz4_uncompress", C.c_int64,
              [C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint8),
               C.c_uint64])
-    src = (C.c_uint8 * len(data)).from_buffer_copy(data)
-    dst = (C.c_uint8 * cap)()
-    n = f(src, len(data), dst, cap)
+    n, dst = _uncompress_guarded(f, data, cap, guard)
     if n < 0:
         raise RuntimeError("lz4_uncompress failed")
     return bytes(dst[:n])

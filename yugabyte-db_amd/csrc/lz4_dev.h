@@ -14,8 +14,15 @@
 //   length - 4; nibble 15 extends with 255-bytes + terminator byte;
 //   literals; 2-byte LE match offset (>= 1); match copies may overlap
 //   (byte-ordered copy). The final sequence holds literals only.
-// Parity is pinned by byte-exact round-trip tests across the three
-// compilations (host compressor feeding host + device decompressors).
+// The decoder is pinned by an independent restatement of the format
+// (tests/codec_cases.py): a pure-Python reference decoder, an encoder that
+// emits length extensions on both sides of one and two 255 bytes,
+// zero-literal sequences, offsets 1 .. 3 and 65535 and an empty final
+// sequence (a census the tests assert), and malformed streams for every
+// bounds check below — on the host with an exact capacity and guard bytes
+// (tests/test_codec_streams.py, make codec_sim_asan), on the device through
+// feed_sst (tests/test_codec_streams_gpu.py). The compressor below is
+// checked against the same reference decoder.
 #ifndef YBG_LZ4_DEV_H
 #define YBG_LZ4_DEV_H
 
@@ -68,6 +75,9 @@ LZ4DEV int64_t lz4_uncompress(const uint8_t* src, uint64_t n, uint8_t* dst,
     const uint8_t* m = dst + op - off;
     for (uint64_t i = 0; i < mlen; ++i) dst[op + i] = m[i];  // may overlap
     op += mlen;
+    // a block never ends on a match: the final sequence is literals only
+    // (possibly none, token 0x00)
+    if (ip >= n) return -1;
   }
   return (int64_t)op;
 }

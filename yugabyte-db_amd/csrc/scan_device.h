@@ -3819,8 +3819,11 @@ DEV bool scan_one_interval(const DevSpec& sp, const uint8_t* data,
       }
       rk_len = rk;
       row_open = true;
-      if (EMIT)  // scan position: (interval, entry offset within block)
-        row_sort_key = ((uint64_t)cur_iv << 16) | (uint64_t)(p - blk);
+      if (EMIT)  // scan position: (interval, entry offset within block);
+                 // offsets are 32-bit (Interval), blocks may exceed 64 KB.
+                 // Holds while cur_iv < 2^32 (Interval::block is 32-bit
+                 // too; 2^32 restart intervals are ~2^36 entries)
+        row_sort_key = ((uint64_t)cur_iv << 32) | (uint64_t)(p - blk);
       row_reset(&rc, sp);
     }
     if (iv_flags && crossed && !row_change) iv_flags[cur_iv] = 1;

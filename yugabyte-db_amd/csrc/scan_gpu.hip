@@ -1767,6 +1767,8 @@ int yb_gpu_scan_feed_sst(ybg_scan_t* s, const uint8_t* file, uint64_t size,
         if (!(b & 0x80)) break;
         shift += 7;
       }
+      if (ulen >> 32)  // a varint32 holds 32 bits, not the 35 of 5 bytes
+        return set_err(3, "corrupt compressed-block length preamble");
       un_len[i] = ulen;
     } else {
       un_len[i] = szs[i];

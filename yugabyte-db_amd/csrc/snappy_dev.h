@@ -16,9 +16,16 @@
 //     10 copy, 2-byte offset: len = (tag>>2)+1, off = 2-byte LE
 //     11 copy, 4-byte offset: len = (tag>>2)+1, off = 4-byte LE
 // Copies may overlap their output (RLE-style), so the copy loop is
-// byte-ordered. Parity for this codec is pinned by byte-exact round-trip
-// tests (compressor -> both decompressors) — the reference's own snappy
-// binaries are not available in this container (DESIGN.md "Oracle").
+// byte-ordered. The reference's own snappy binaries are not available
+// (DESIGN.md "Oracle"), so the decoder is pinned by an independent
+// restatement of the format (tests/codec_cases.py): a pure-Python reference
+// decoder, full-format encoders whose streams hold every element kind above
+// (a census the tests assert), and a list of malformed streams for every
+// bounds check below — decoded on the host with an exact capacity and guard
+// bytes (tests/test_codec_streams.py, make codec_sim_asan) and on the
+// device through feed_sst (tests/test_codec_streams_gpu.py). The
+// compressor below emits a subset of the format and is checked against the
+// same reference decoder.
 #ifndef YBG_SNAPPY_DEV_H
 #define YBG_SNAPPY_DEV_H
 
@@ -48,7 +55,8 @@ SNPDEV int64_t snappy_uncompress(const uint8_t* src, uint64_t n,
     if (!(b & 0x80)) break;
     shift += 7;
   }
-  if (ulen > dst_cap) return -1;
+  // a varint32: the fifth byte may carry four more bits, not seven
+  if ((ulen >> 32) || ulen > dst_cap) return -1;
   while (ip < n) {
     uint8_t tag = src[ip++];
     uint32_t kind = tag & 3;
